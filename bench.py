@@ -23,6 +23,18 @@ under "weak" (``--split weak`` makes it the headline; ``--no-weak`` skips it).
 
     python bench.py [--gpus N --steps K --warmup W]   (N > 1: starts N ranks itself)
     torchrun --nproc-per-node N bench.py --gpus N ...  (--gpus must equal the world size)
+
+A plain run does what the headline figure needs and no more: it builds the
+batch, warms up, times the K steps and prints the result line.  ``--full`` adds
+everything else the benchmark measures, each at the cost of runs of its own:
+the roofline of the dominant kernel (an untimed step for the algorithmic
+bytes, HIP events around the ingest launch of every timed step, the PMC
+traffic profile), the host-engine and pure-Python CPU baselines with their
+parity check of the GPU quantiles, and for N > 1 the weak line beside the
+strong one.  ``--dump-outputs DIR`` writes what the last timed step returned
+to its caller (the quantiles of every stream of this rank) under DIR as
+float64 ``.npy`` files; with the same arguments the inputs, and so these
+files, are the same from run to run.
 """
 import argparse
 import json
@@ -56,12 +68,19 @@ def parse():
     ap.add_argument("--values", type=int, default=None, help="override: values per stream (cfg4: total)")
     ap.add_argument("--eps", type=float, default=None, help="default 0.01 (cfg5: 0.001)")
     ap.add_argument("--seed", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline of the dominant "
+                         "kernel, the CPU baselines (see --no-cpu) and, N > 1, the weak line beside the strong one")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the quantiles the last timed step returned to "
+                         "DIR/quantiles.npy (N > 1: quantiles_rank<r>.npy; a split's stream ids in stream_ids*.npy), float64; "
+                         "beyond 64 MB a fixed seeded sample of the streams, their ids in quantiles_rows.npy")
     ap.add_argument("--cpu-sample", type=int, default=1_000_000,
-                    help="streams of the same workload timed on the host engine (rank 0, N=1); "
+                    help="--full: streams of the same workload timed on the host engine (rank 0, N=1); "
                          "default: the whole cfg3 batch")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0 = the CPUs this process may use (capped by OMP_NUM_THREADS if set)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--cpu-all-cores", action="store_true",
                     help="also time the host engine on every CPU of the affinity set (beyond this job's share)")
     ap.add_argument("--exchange", default="allgather", choices=["allgather", "alltoall"],
@@ -69,7 +88,7 @@ def parse():
     ap.add_argument("--split", default="auto", choices=["auto", "strong", "weak"],
                     help="N > 1, cfg2/3/5: strong = split the one batch over the ranks by stream "
                          "(the metric's configuration; the default), weak = every rank its own batch")
-    ap.add_argument("--no-weak", action="store_true", help="N > 1 strong: skip the weak line beside it")
+    ap.add_argument("--no-weak", action="store_true", help="N > 1 strong, --full: skip the weak line beside it")
     ap.add_argument("--proxy", type=int, default=0, metavar="N",
                     help="one process, one GPU: run only rank --proxy-rank's share of the N-way strong split "
                          "(the single-GPU proxy of an N-GPU run; DESIGN 7)")
@@ -229,7 +248,7 @@ def cpu_baseline(x, offs, sample, threads, eps, gpu_q, py_streams=2000, all_core
     else:
         out["all_cores"] = dict(value=None, cores=aff, estimate=nv / dt / threads * aff,
                                 note="not run by default (the box allots %d CPUs to this job); estimate = "
-                                     "per-thread rate x %d CPUs, bench.py --cpu-all-cores measures it"
+                                     "per-thread rate x %d CPUs, bench.py --full --cpu-all-cores measures it"
                                      % (threads, aff))
     return out
 
@@ -271,6 +290,32 @@ def rank_streams(workload, offs, world, rank):
     return torch.arange(a, b, dtype=torch.int64)
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(d, q, idx, rank, world):
+    """--dump-outputs: the array the timed path returned in its last step (the
+    quantiles of this rank's streams, one row per stream) as float64 .npy
+    files under `d`, at most DUMP_LIMIT_BYTES in all.  A larger result is cut
+    to a fixed sample of its rows (numpy default_rng(0), ascending), whose row
+    numbers go beside it: the same rows in every run of the same arguments."""
+    os.makedirs(d, exist_ok=True)
+    tag = "" if world == 1 else "_rank%d" % rank
+    qn = np.ascontiguousarray(q.detach().cpu().numpy(), dtype=np.float64)
+    qn = qn.reshape(qn.shape[0], -1) if qn.ndim else qn.reshape(1, 1)
+    ids = None if idx is None else np.asarray(idx.cpu().numpy(), dtype=np.float64)
+    row_bytes = 8 * (qn.shape[1] + (1 if ids is not None else 0))
+    if qn.shape[0] * row_bytes > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(qn.shape[0], size=keep, replace=False))
+        qn = qn[rows]
+        ids = None if ids is None else ids[rows]
+        np.save(os.path.join(d, "quantiles_rows%s.npy" % tag), rows.astype(np.float64))
+    np.save(os.path.join(d, "quantiles%s.npy" % tag), qn)
+    if ids is not None:
+        np.save(os.path.join(d, "stream_ids%s.npy" % tag), ids)
+
+
 def free_port():
     import socket
     with socket.socket() as sk:
@@ -299,6 +344,8 @@ def main():
     rehearse = os.environ.get("GK_BENCH_REHEARSE") == "1" or not on_gpu
     if a.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if a.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
     if on_gpu and not rehearse and a.gpus > torch.cuda.device_count():
         sys.exit("bench.py: --gpus %d but this node has %d GPU(s) (GK_BENCH_REHEARSE=1 shares them)"
                  % (a.gpus, torch.cuda.device_count()))
@@ -401,7 +448,7 @@ def main():
                 nw += extra
         gsync()
         warm_info["steps"], warm_info["seconds"] = nw, time.perf_counter() - tw
-        for t_ss in timed_sets:
+        for t_ss in timed_sets:  # (--full only: the roofline's launch events)
             t_ss.timing(True, stats=os.environ.get("GK_BENCH_STATS_TIMING") == "1")
             t_ss.read_timing()
         barrier()
@@ -475,16 +522,19 @@ def main():
             # enqueued without a host synchronisation (the timed region syncs at its end)
             return ss.ingest(x, offs, quantiles=qs, sync=False)
 
-    # algorithmic bytes of one k_ingest_small launch (untimed identical step)
-    timed_sets = [ss]
-    if a.workload == "cfg4" and K > 1:
+    # --full: algorithmic bytes of one k_ingest_small launch (untimed identical
+    # step) and the launch's own events in the timed steps, for the roofline
+    timed_sets = []
+    bytes_per_launch = None
+    if a.full and a.workload == "cfg4" and K > 1:
         # one shard's ingest launch (before the merges flush the sets)
         sets[0].reset()
         sets[0].ingest(shards[0][0], shards[0][1])
         bytes_per_launch = algorithmic_bytes(sets[0], S, S * L, 0)
         timed_sets = sets
         step()
-    else:
+    elif a.full:
+        timed_sets = [ss]
         step()
         bytes_per_launch = algorithmic_bytes(ss, S_loc, N, len(qs) if a.workload != "cfg4" else 0)
 
@@ -494,7 +544,10 @@ def main():
         np.savez("%s.rank%d.npz" % (a.dump, rank), q=q.cpu().numpy(),
                  idx=(idx if idx is not None else torch.arange(S_loc)).numpy())
 
-    traffic, traffic_src = pmc_traffic(a.workload)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, q, idx, rank, world)  # (idx: a strong split's or proxy's stream ids)
+
+    traffic, traffic_src = pmc_traffic(a.workload) if a.full else (None, None)
     if traffic is not None and (not on_gpu or S_loc != defaults[a.workload][0] or
                                 (a.workload != "cfg5" and L != defaults[a.workload][1])):
         traffic, traffic_src = None, "the PMC profile is of the whole single-GPU workload, not this batch"
@@ -502,16 +555,17 @@ def main():
     value = total_values / dt
     ms_step = dt / a.steps * 1e3
     k_ms = flush_ms / max(launches, 1)
-    achieved = bytes_per_launch / (k_ms * 1e-3) / 1e9 if k_ms > 0 else None
+    achieved = bytes_per_launch / (k_ms * 1e-3) / 1e9 if a.full and k_ms > 0 else None
     ratio = traffic / bytes_per_launch if traffic else None
     per_rank = None
     n_ranks = world
     if world > 1:
+        import torch.distributed as dist
+        n_ranks = dist.get_world_size()  # the ranks that joined the process group
+    if world > 1 and a.full:
         # every rank's own launch time and algorithmic bytes; the headline
         # roofline is the SLOWEST rank's launch on that rank's bytes (the node
         # rate is bound by it), the others are listed beside it
-        import torch.distributed as dist
-        n_ranks = dist.get_world_size()  # the ranks that joined the process group
         mine = {"rank": rank, "device": str(dev), "streams": S_loc, "values": N, "launch_ms": k_ms,
                 "bytes_per_launch": bytes_per_launch,
                 "frac": (bytes_per_launch / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if k_ms > 0 else None}
@@ -581,6 +635,9 @@ def main():
                                          if os.environ.get("GK_BENCH_STATS_TIMING") == "1" else None)},
         "library": _library_identity(),
     }
+    if not a.full:
+        line["roofline"] = {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s", "achieved": None, "frac": None,
+                            "note": "not measured by a plain run: bench.py --full"}
     if per_rank is not None:
         line["roofline"]["rank"] = slow["rank"]
         line["roofline"]["per_rank"] = per_rank
@@ -588,7 +645,7 @@ def main():
                                     "launch on that rank's own bytes; every rank under per_rank")
     if not on_gpu:
         line["device"] = "cpu (host engine libgkarray_cpu.so): a split check, not a GPU number"
-    if world > 1 and split == "strong" and not a.no_weak:
+    if a.full and world > 1 and split == "strong" and not a.no_weak:
         # the weak line beside it: every rank its own whole batch (seed + rank)
         del ss, x, offs, q
         xw, ow = make_batch((5 if a.workload == "cfg5" else a.seed) + rank)
@@ -605,7 +662,7 @@ def main():
         line["weak"] = {"value": tot_w / dtw, "ms_per_step": dtw / a.steps * 1e3, "scaling": "weak",
                         "streams_per_gpu": S, "launch_ms": fw / max(lw, 1),
                         "note": "every rank its own %d-stream batch (seed + rank), same K/W" % S}
-    if rank == 0 and world == 1 and on_gpu and not a.no_cpu and a.workload != "cfg4":
+    if a.full and rank == 0 and world == 1 and on_gpu and not a.no_cpu and a.workload != "cfg4":
         threads = a.cpu_threads or host_cores()[0]
         sample = min(a.cpu_sample, S)
         if a.workload == "cfg5":  # the long streams dominate: a bounded prefix of streams

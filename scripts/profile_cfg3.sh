@@ -2,9 +2,11 @@
 # bench command, then separate PMC passes (FETCH_SIZE, WRITE_SIZE, SQ) on the
 # same workload.  Counters are collected without any tracing domain.
 cd $GRAFT_REPO_ROOT
+# logs and tables go under $OUT (default bench_out/, git-ignored)
+export OUT=${OUT:-bench_out}; mkdir -p "$OUT"
 export TMPDIR=/tmp
 TAG=${1:-r01}
-D=gpurun_out/prof_$TAG
+D=$OUT/prof_$TAG
 mkdir -p $D
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $D/trace -o run -- \
   python3 bench.py --no-cpu --steps 5 --warmup 2 > $D/bench_trace.log 2>&1 || exit $?

@@ -15,9 +15,10 @@ SURVEY.md section 8(c):
   gk:72 (the reference as written raises AttributeError on plain floats at its
   first flush).
 
-Outputs ``tests/golden/golden.npz`` (arrays only; load with
-``allow_pickle=False``) and ``tests/golden/golden_index.json`` (case metadata).
-Both files are data: inputs and the reference's outputs on them.
+Outputs ``tests/golden/golden_NN.npz`` (arrays only, in parts of under 1 MiB
+written by ``golden_io.save_arrays``; load with ``allow_pickle=False``) and
+``tests/golden/golden_index.json`` (case metadata).
+These files are data: inputs and the reference's outputs on them.
 """
 import importlib.util
 import json
@@ -357,14 +358,16 @@ def main():
                                          plan=list(plan)))
                     cid += 1
 
-    np.savez_compressed(os.path.join(HERE, "golden.npz"), **st.arrays)
+    sys.path.insert(0, os.path.dirname(HERE))
+    import golden_io
+    parts = golden_io.save_arrays(st.arrays, HERE)
     with open(os.path.join(HERE, "golden_index.json"), "w") as f:
         json.dump(dict(cases=st.index, kat=kat, qs=QS, qs_unsorted=QS_UNSORTED,
                        qs_oor=QS_OOR, generator="tests/golden/make_golden.py",
                        reference="gkarray.py (githomin/sketches-py) via SURVEY 8(c) shim",
                        numpy=np.__version__), f, indent=0)
     print("cases:", cid, "arrays:", len(st.arrays),
-          "bytes:", os.path.getsize(os.path.join(HERE, "golden.npz")))
+          "bytes:", [os.path.getsize(p) for p in parts])
 
 
 if __name__ == "__main__":

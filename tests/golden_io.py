@@ -1,7 +1,13 @@
-"""Loader for the committed golden vectors (tests/golden/*, made by make_golden.py)."""
+"""Loader for the committed golden vectors (tests/golden/*, made by make_golden.py).
+
+The arrays are kept in several files, golden_00.npz, golden_01.npz, ..., each
+under 1 MiB (no committed file may be larger); a case's arrays stay together
+and the cases keep their order."""
 import functools
+import glob
 import json
 import os
+import re
 
 import numpy as np
 
@@ -17,8 +23,48 @@ def index():
 
 @functools.lru_cache(maxsize=1)
 def arrays():
-    with np.load(os.path.join(GOLDEN_DIR, "golden.npz"), allow_pickle=False) as z:
-        return {k: z[k] for k in z.files}
+    out = {}
+    parts = sorted(glob.glob(os.path.join(GOLDEN_DIR, "golden_[0-9][0-9].npz")))
+    assert parts, "no golden vectors under %s" % GOLDEN_DIR
+    for p in parts:
+        with np.load(p, allow_pickle=False) as z:
+            for k in z.files:
+                assert k not in out, "%s: %s is in an earlier part too" % (p, k)
+                out[k] = z[k]
+    return out
+
+
+PART_LIMIT_BYTES = 1 << 20  # of one committed file
+
+
+def save_arrays(arrays, directory=GOLDEN_DIR, target=640 * 1024):
+    """Write `arrays` ("case<id>/..." -> array) as golden_NN.npz parts (make_golden.py).
+    A part is closed once the .npy bytes it holds, deflated, with the zip's
+    per-entry cost, are estimated at `target`; the real sizes are checked."""
+    import zlib
+    for p in glob.glob(os.path.join(directory, "golden_[0-9][0-9].npz")):
+        os.remove(p)
+    by_case = {}
+    for k in arrays:
+        by_case.setdefault(int(re.match(r"case(\d+)/", k).group(1)), []).append(k)
+    parts, cur, size = [], {}, 0
+    for cid in sorted(by_case):
+        est = sum(len(zlib.compress(np.ascontiguousarray(arrays[k]).tobytes(), 6)) + 2 * len(k) + 260
+                  for k in by_case[cid])
+        if cur and size + est > target:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur.update((k, arrays[k]) for k in by_case[cid])
+        size += est
+    if cur:
+        parts.append(cur)
+    assert len(parts) <= 100
+    paths = []
+    for i, part in enumerate(parts):
+        paths.append(os.path.join(directory, "golden_%02d.npz" % i))
+        np.savez_compressed(paths[-1], **part)
+        assert os.path.getsize(paths[-1]) < PART_LIMIT_BYTES, paths[-1]
+    return paths
 
 
 def get(cid, name):

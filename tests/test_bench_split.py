@@ -36,7 +36,8 @@ def run_bench(args, world, dump, env_extra=None, launcher="torchrun"):
     else:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=%d" % world,
                "--master-addr=127.0.0.1", "--master-port=%d" % free_port(), BENCH]
-    cmd += args + ["--gpus", str(world), "--steps", "1", "--warmup", "0", "--no-cpu", "--dump", dump]
+    # --full: the weak line beside the strong one and roofline.per_rank are checked below
+    cmd += args + ["--gpus", str(world), "--steps", "1", "--warmup", "0", "--full", "--no-cpu", "--dump", dump]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
