@@ -34,7 +34,7 @@
  *    buffers alive and unchanged until the set's next call or gk_sync: a
  *    stream that needs a class whose arena has no free slot yet is deferred
  *    and re-run from them by the host runtime before the next call proceeds.
- *    gk_merge,
+ *    gk_merge, gk_rollup,
  *    gk_merge_compress, gk_import, gk_save / gk_load and gk_num_promoted
  *    synchronise before returning.
  *  - Limits.  Any finite eps > 0 with int(1/eps)+1 < 2^24 is accepted (the
@@ -139,6 +139,44 @@ int gk_stats(gk_set* set, int64_t* n, double* mn, double* mx, double* sum,
  * its merges).  Returns GK_E_EPS_MISMATCH if any eps differs (gk:118-119) or
  * GK_E_ARG if the stream counts differ. */
 int gk_merge(gk_set* dst, gk_set* const* srcs, int nsrcs, void* stream);
+
+/* Group-by roll-up: GKArray.merge (gk:111-154) of groups of `src`'s streams
+ * into the streams of `dst`, a DIFFERENT set with the same eps (stream counts
+ * may differ: dst has G streams, src has S).  `group_offsets` (int64[G+1],
+ * non-decreasing, starting at 0) and `members` (int64[group_offsets[G]],
+ * indices into src) give the groups in CSR form; the arrays are device memory
+ * for the GPU engine, host memory for the CPU engine.  For every destination
+ * stream j, in order of k:
+ *     for k in group_offsets[j] .. group_offsets[j+1]-1:
+ *         dst[j].merge(src[members[k]])
+ *  - dst keeps its state from before the call (a roll-up can be continued by
+ *    a later call); pending values of dst join the first merge's incoming
+ *    list (gk:71-72).  A destination with an empty group is not touched at
+ *    all (not flushed).
+ *  - Members are mutated as the reference mutates `other`: a member with
+ *    n == 0 is left alone and the destination runs merge_compress()
+ *    (gk:121-123); any other member is flushed unconditionally (gk:126 /
+ *    gk:137) before it is converted, and spread uses its n (gk:136).  Source
+ *    streams that are no member stay bit-identical.
+ *  - _sum/_avg are not merged, except by the copy branch of a destination
+ *    with n == 0 (gk:125-133), which may be taken mid-fold when the earlier
+ *    members were all empty.
+ *  - GK_E_ARG, before anything is mutated: dst == src, NULL arrays,
+ *    group_offsets not starting at 0 or decreasing, a member outside [0, S),
+ *    a source stream listed more than once (a repeated `other` would need a
+ *    re-flush between its merges).  GK_E_EPS_MISMATCH if eps differs
+ *    (gk:118-119).
+ *  - GK_E_OVERFLOW, two cases.  A member whose own flush outgrows the last
+ *    capacity class: that member keeps its state, the other members have been
+ *    flushed, no destination is touched.  A destination that outgrows the
+ *    last class or the count limit: every member has been flushed, such a
+ *    destination holds the fold of the members before the one that did not
+ *    fit (table, n, _min, _max consistent with each other), every other
+ *    destination is complete.
+ * Synchronises before returning, after settling earlier asynchronous work
+ * (and errors) of both sets. */
+int gk_rollup(gk_set* dst, gk_set* src, const int64_t* group_offsets,
+              const int64_t* members, void* stream);
 
 /* GKArray.merge_compress(entries) with an explicit entry list (gk:63-109,
  * gk:71): stream s merges extra records [eoffs[s], eoffs[s+1]) given as

@@ -578,6 +578,41 @@ int gk_merge(gk_set* dst, gk_set* const* srcs, int nsrcs, void* stream) {
   return GK_OK;
 }
 
+int gk_rollup(gk_set* dst, gk_set* src, const int64_t* group_offsets, const int64_t* members, void* stream) {
+  (void)stream;
+  int rc = check_set(dst);
+  if (!rc) rc = check_set(src);
+  if (rc) return rc;
+  if (dst == src) return fail(GK_E_ARG, "roll-up of a set into itself");
+  if (!group_offsets) return fail(GK_E_ARG, "group_offsets is null");
+  if (src->eps != dst->eps)  // gk:118-119
+    return fail(GK_E_EPS_MISMATCH, "Cannot merge two GKArrays with different epsilon values");
+  const int64_t G = dst->S, S = src->S;
+  if (group_offsets[0] != 0) return fail(GK_E_ARG, "group_offsets must start at 0");
+  for (int64_t j = 0; j < G; ++j)
+    if (group_offsets[j + 1] < group_offsets[j])
+      return fail(GK_E_ARG, "group_offsets decrease at group %lld", (long long)j);
+  const int64_t M = group_offsets[G];
+  if (M > 0 && !members) return fail(GK_E_ARG, "members is null");
+  // every member in [0, S) and listed once: nothing is mutated before this holds
+  std::vector<bool> seen((size_t)S, false);
+  for (int64_t k = 0; k < M; ++k) {
+    const int64_t m = members[k];
+    if (m < 0 || m >= S)
+      return fail(GK_E_ARG, "member %lld (position %lld) outside [0, %lld)", (long long)m, (long long)k, (long long)S);
+    if (seen[(size_t)m]) return fail(GK_E_ARG, "source stream %lld is listed more than once", (long long)m);
+    seen[(size_t)m] = true;
+  }
+  // per destination stream the left fold dst[j].merge(src[members[k]]) in
+  // order of k (gk:111-154); an empty group leaves its destination untouched
+  parallel_for(G, dst->threads, [&](int64_t j) {
+    std::vector<Rec> conv;
+    for (int64_t k = group_offsets[j]; k < group_offsets[j + 1]; ++k)
+      merge_stream(dst, dst->st[j], src->st[members[k]], conv);
+  });
+  return GK_OK;
+}
+
 int gk_merge_compress(gk_set* h, const double* v, const int32_t* g, const int32_t* d, const int64_t* eoffs,
                       void* stream) {
   (void)stream;

@@ -147,6 +147,7 @@ struct gk_set {
   // gk_fold_packed: receives the packed states merged into this set (made on first use)
   gk_set* fold_scratch = nullptr;
   gk_set* self_scratch = nullptr;  // snapshot source of dst.merge(dst), only during that merge
+  int64_t* d_roll_prog = nullptr;  // gk_rollup into this set: the member a resumed fold starts at (first use)
   // Host-walked chains: the gk:52-59 chains of the
   // longest streams run on host cores beside the GPU ingest.  hc_min: shortest
   // stream taken (0: off; GK_HOST_CHAINS=0 / GK_HOST_CHAIN_MIN); hc_threads:
@@ -1069,7 +1070,8 @@ int run_ingest(gk_set* h, const double* x, const int64_t* offs, int force, hipSt
 
 // Merge / explicit merge_compress at LDS capacity level 0, then the streams
 // that did not fit at increasing levels (their class raised on the device).
-// Synchronous (one readback per level).
+// Synchronous (one readback per level).  base.list / base.count (optional):
+// only these streams instead of every stream.
 int run_merge(gk_set* dst, const MergeArgsHost& base, hipStream_t s) {
   MergeArgsHost a = base;
   const GKPoolDev pool = pool_args(dst);
@@ -1088,8 +1090,8 @@ int run_merge(gk_set* dst, const MergeArgsHost& base, hipStream_t s) {
     }
     a.dst = dst->st;
     a.cap = cap;
-    a.list = level == 0 ? nullptr : ovf_list(dst, level - 1);
-    a.count = level == 0 ? dst->S : todo;
+    a.list = level == 0 ? base.list : ovf_list(dst, level - 1);
+    a.count = level == 0 ? (base.list ? base.count : dst->S) : todo;
     a.ovf_count = ovf_count(dst, level);
     a.ovf_list = ovf_list(dst, level);
     if (cap > kMaxLdsCap) {
@@ -1110,6 +1112,63 @@ int run_merge(gk_set* dst, const MergeArgsHost& base, hipStream_t s) {
   }
   return fail(GK_E_OVERFLOW, "%lld stream(s) exceed %d table entries in merge, or the per-stream count limit "
               "2*eps*(n-1) <= 2^30", (long long)todo, dst->st.cap[dst->st.nclass - 1]);
+}
+
+// The roll-up fold (k_rollup) at capacity level 0, then the destinations whose
+// fold stopped at a member that did not fit, at increasing levels: their class
+// is raised and the fold resumes at the recorded member (run_merge's scheme).
+// Synchronous (one readback per level).
+int run_rollup(gk_set* dst, const gk_set* src, const int64_t* goffs, const int64_t* members, hipStream_t s) {
+  if (!dst->d_roll_prog &&
+      hipMalloc(&dst->d_roll_prog, (size_t)std::max<int64_t>(dst->S, 1) * sizeof(int64_t)) != hipSuccess) {
+    dst->d_roll_prog = nullptr;
+    return fail(GK_E_NOMEM, "roll-up progress array of %lld entries failed", (long long)dst->S);
+  }
+  RollupArgsHost a{};
+  a.src = src->st;
+  a.goffs = goffs;
+  a.members = members;
+  a.progress = dst->d_roll_prog;
+  const GKPoolDev pool = pool_args(dst);
+  int64_t todo = 0;
+  dst->ctr_clean = false;
+  HIP_TRY(hipMemsetAsync(dst->d_ovfc, 0, kRounds * sizeof(int32_t), s));
+  for (int level = 0; level < dst->st.nclass; ++level) {
+    const int cap = dst->st.cap[level];
+    if (level > 0) {
+      if (todo == 0) return GK_OK;
+      // destinations below this class move up so that their fold may go on
+      int rc = grow_class(dst, level, (int64_t)dst->st.alloc[level] + todo, s);
+      if (rc) return rc;
+      dst->no_members = false;
+      HIP_TRY(gk_launch_promote_dev(dst->st, ovf_count(dst, level - 1), ovf_list(dst, level - 1), level, pool, s));
+    }
+    a.dst = dst->st;
+    a.cap = cap;
+    a.resume = level > 0;
+    a.list = level == 0 ? nullptr : ovf_list(dst, level - 1);
+    a.count = level == 0 ? dst->S : todo;
+    a.ovf_count = ovf_count(dst, level);
+    a.ovf_list = ovf_list(dst, level);
+    if (cap > kMaxLdsCap) {
+      int rc = ensure_ws(dst, level);
+      if (rc) return rc;
+      a.ws = dst->d_ws[level];
+      a.ws_bytes = dst->ws_bytes[level];
+      a.ws_blocks = dst->ws_blocks[level];
+    } else {
+      a.ws = nullptr;
+      a.ws_bytes = 0;
+      a.ws_blocks = 0;
+    }
+    HIP_TRY(gk_launch_rollup(a, s));
+    todo = read_overflow(dst, level, s);
+    if (todo < 0) return (int)todo;
+    if (todo == 0) return GK_OK;
+  }
+  return fail(GK_E_OVERFLOW, "%lld destination stream(s) exceed %d table entries in roll-up, or the per-stream count "
+              "limit 2*eps*(n-1) <= 2^30: they hold the fold of the members before the one that did not fit",
+              (long long)todo, dst->st.cap[dst->st.nclass - 1]);
 }
 
 }  // namespace
@@ -1355,7 +1414,7 @@ int gk_destroy(gk_set* h) {
                   st.avg,     st.cls,        st.slot,        st.pbuf,        h->d_qs,
                   h->d_ctr,   h->d_zero_offs, h->d_long_list, h->d_long_n,
                   h->ps.list_ws, h->ps.list_b0, h->ps.ws,    h->ps.ws_need,  st.rtab,        st.n0,
-                  h->d_defer, h->d_hc,       h->d_hc_count,  h->d_hc_fail};
+                  h->d_defer, h->d_hc,       h->d_hc_count,  h->d_hc_fail,   h->d_roll_prog};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (int c = 0; c < GK_MAX_CLASSES; ++c)
@@ -1608,6 +1667,79 @@ int gk_merge(gk_set* dst, gk_set* const* srcs, int nsrcs, void* stream) {
     rc = run_merge(dst, a, s);
     if (rc) return rc;
   }
+  HIP_TRY(hipStreamSynchronize(s));
+  return GK_OK;
+}
+
+int gk_rollup(gk_set* dst, gk_set* src, const int64_t* group_offsets, const int64_t* members, void* stream) {
+  int rc = check_set(dst);
+  if (!rc) rc = check_set(src);
+  if (rc) return rc;
+  if (dst == src) return fail(GK_E_ARG, "roll-up of a set into itself");
+  if (!group_offsets) return fail(GK_E_ARG, "group_offsets is null");
+  if (src->eps != dst->eps)  // gk:118-119
+    return fail(GK_E_EPS_MISMATCH, "Cannot merge two GKArrays with different epsilon values");
+  if (src->device != dst->device) return fail(GK_E_ARG, "the sets live on different devices");
+  hipStream_t s = (hipStream_t)stream;
+  rc = gk_sync(dst, stream);
+  if (!rc) rc = gk_sync(src, stream);
+  if (rc) return rc;
+  const int64_t G = dst->S, S = src->S;
+  // ---- argument checks on the device, read back before anything is mutated.
+  // Scratch of src that no launch of this call uses otherwise: the last
+  // overflow list (S words) holds the bitmap, then the flush list; its count
+  // word the error bits, then the flush count.
+  int32_t* const word = ovf_count(src, kRounds - 1);
+  int32_t* const scratch = ovf_list(src, kRounds - 1);
+  src->ctr_clean = false;
+  HIP_TRY(hipMemsetAsync(word, 0, sizeof(int32_t), s));
+  HIP_TRY(gk_launch_rollup_check_offsets(group_offsets, G, word, s));
+  int64_t* const h_total = reinterpret_cast<int64_t*>(src->h_ovf + 2);
+  HIP_TRY(hipMemcpyAsync(h_total, group_offsets + G, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  rc = (int)read_overflow(src, kRounds - 1, s);
+  if (rc < 0) return rc;
+  if (rc != 0) return fail(GK_E_ARG, "group_offsets must start at 0 and not decrease");
+  const int64_t M = *h_total;
+  if (M == 0) return GK_OK;  // every group is empty: nothing is touched
+  if (!members) return fail(GK_E_ARG, "members is null");
+  if (M > S)
+    return fail(GK_E_ARG, "%lld members of %lld source streams: a stream is listed more than once or out of range",
+                (long long)M, (long long)S);
+  HIP_TRY(hipMemsetAsync(scratch, 0, (size_t)((S + 31) / 32) * sizeof(uint32_t), s));
+  HIP_TRY(gk_launch_rollup_check_members(members, M, S, reinterpret_cast<uint32_t*>(scratch), word, s));
+  rc = (int)read_overflow(src, kRounds - 1, s);
+  if (rc < 0) return rc;
+  if (rc & 2) return fail(GK_E_ARG, "a member lies outside [0, %lld)", (long long)S);
+  if (rc & 4) return fail(GK_E_ARG, "a source stream is listed more than once");
+  // ---- other.merge_compress() of every member with n != 0 (gk:126 / gk:137;
+  // unconditional there, pending values or not)
+  if (M == S) {
+    // every source stream is a member (the plain group-by): the batch flush
+    // that gk_merge gives its sources; on a stream with n == 0 it changes nothing
+    rc = begin_call(src, s);
+    if (!rc) rc = run_ingest(src, nullptr, nullptr, 2, s);
+    if (!rc) rc = mark_done(src, s);
+    if (!rc) rc = gk_sync(src, stream);
+    if (rc) return rc;
+  } else {
+    // k_merge's explicit-record mode with no records, over the list of those
+    // members; members that need a larger class for it climb run_merge's levels
+    HIP_TRY(gk_launch_rollup_flush_list(src->st, members, M, word, scratch, s));
+    const int64_t nflush = read_overflow(src, kRounds - 1, s);
+    if (nflush < 0) return (int)nflush;
+    if (nflush > 0) {
+      MergeArgsHost a{};
+      a.src = src->st;
+      a.eoffs = src->d_zero_offs;
+      a.mode = 1;
+      a.list = scratch;
+      a.count = nflush;
+      rc = run_merge(src, a, s);
+      if (rc) return rc;
+    }
+  }
+  rc = run_rollup(dst, src, group_offsets, members, s);
+  if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(s));
   return GK_OK;
 }

@@ -4763,6 +4763,239 @@ __device__ __forceinline__ void flag_overflow(int32_t* cnt, int32_t* list, int64
 
 #define GK_MERGE_RANK_MAX 256  // pending values ranked by comparison up to this many; bitonic above
 
+// The steps of one merge, shared by k_merge and k_rollup.  All of them work on
+// the arrays of a MergeLDS carve (LDS or a block's global workspace).
+
+// gk:136-147: the converted records of a flushed `other` table into rv/rg/rd
+//   (other._min, g0+d0-spread-1), (v_k, g_{k+1}+d_{k+1}-d_k),
+//   (v_{L-1}, spread+1-d_{L-1}); only g > 0 is kept.  Returns their number
+//   (at most oE + 1, which the caller has checked against the carve).
+__device__ __forceinline__ int merge_convert(const MergeLDS& m, const GKRec* __restrict__ otab, int oE,
+                                             int64_t spread, double omn, int lane) {
+  const int ncand = oE + 1;
+  int base = 0;
+  for (int c0 = 0; c0 < ncand; c0 += 64) {
+    const int c = c0 + lane;
+    int64_t gv = 0;
+    double vv = 0.0;
+    if (c < ncand) {
+      if (c == 0) {
+        gv = (int64_t)otab[0].g + otab[0].d - spread - 1;
+        vv = omn;
+      } else if (c < oE) {
+        gv = (int64_t)otab[c].g + otab[c].d - otab[c - 1].d;
+        vv = otab[c - 1].v;
+      } else {
+        gv = spread + 1 - otab[oE - 1].d;
+        vv = otab[oE - 1].v;
+      }
+    }
+    const bool keep = (c < ncand) && gv > 0;
+    const unsigned long long bal = __ballot(keep);
+    const int before = __popcll(bal & ((1ull << lane) - 1ull));
+    if (keep) {
+      m.rv[base + before] = vv;
+      m.rg[base + before] = (int32_t)gv;
+      m.rd[base + before] = 0;
+    }
+    base += __popcll(bal);
+  }
+  return base;
+}
+
+// stable order of self's raw pending values (gk:72) into sp; ov/og are scratch
+__device__ __forceinline__ void merge_sort_pending(const MergeLDS& m, const double* __restrict__ pb, int p, int lane) {
+  if (p <= GK_MERGE_RANK_MAX) {
+    // few values: each lane ranks its values against all of them
+    for (int i = lane; i < p; i += 64) m.ov[i] = pb[i];
+    __syncthreads();
+    for (int i = lane; i < p; i += 64) {
+      const double x = m.ov[i];
+      int rk = 0;
+      for (int t = 0; t < p; ++t) {
+        const double y = m.ov[t];
+        rk += (y < x) || (y == x && t < i);
+      }
+      m.sp[rk] = x;
+    }
+  } else {
+    // a large flush period (eps < 1/256): bitonic sort of (value, index)
+    // in the output arrays (free here; cap >= pow2 above p for every class)
+    int N = 1;
+    while (N < p) N <<= 1;
+    for (int i = lane; i < N; i += 64) {
+      m.ov[i] = i < p ? pb[i] : __longlong_as_double(0x7ff0000000000000LL);
+      m.og[i] = i < p ? i : INT32_MAX;
+    }
+    __syncthreads();
+    for (int k = 2; k <= N; k <<= 1) {
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int pp = lane; pp < N / 2; pp += 64) {
+          const int i = ((pp & ~(j - 1)) << 1) | (pp & (j - 1));
+          const int l = i + j;
+          const double a = m.ov[i], b = m.ov[l];
+          const int ia = m.og[i], ib = m.og[l];
+          const bool a_gt = (a > b) || (a == b && ia > ib);
+          if (a_gt == ((i & k) == 0)) {
+            m.ov[i] = b;
+            m.ov[l] = a;
+            m.og[i] = ib;
+            m.og[l] = ia;
+          }
+        }
+        __syncthreads();
+      }
+    }
+    for (int i = lane; i < p; i += 64) m.sp[i] = m.ov[i];
+  }
+  __syncthreads();
+}
+
+// merged incoming list: `self.incoming + entries` sorted stably, so on equal
+// values the raw pending values come first (gk:71-72); sp + rv/rg/rd -> iv/ig/id
+__device__ __forceinline__ void merge_incoming(const MergeLDS& m, int p, int nrec, int lane) {
+  for (int r = lane; r < p; r += 64) {
+    const double x = m.sp[r];
+    int lo = 0, hi = nrec;  // records strictly below x
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (m.rv[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    m.iv[r + lo] = x;
+    m.ig[r + lo] = 1;
+    m.id[r + lo] = 0;
+  }
+  for (int t = lane; t < nrec; t += 64) {
+    const double y = m.rv[t];
+    int lo = 0, hi = p;  // pending values <= y
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (m.sp[mid] <= y) lo = mid + 1; else hi = mid;
+    }
+    m.iv[t + lo] = y;
+    m.ig[t + lo] = m.rg[t];
+    m.id[t + lo] = m.rd[t];
+  }
+}
+
+// The four-rule walk of gk:76-106, wave-parallel: table tv/tg/td (E entries)
+// and incoming iv/ig/id (M records) into ov/og/od; *sh_out = the number of
+// output records, or -1 when they exceed outcap (nothing usable written).
+// Incoming records (sorted) fall into gaps: record i precedes entry j iff
+// iv[i] < tv[j] (gk:93), so gap j holds [a_{j-1}, a_j) with a_j = #{i :
+// iv[i] < tv[j]}, and the tail [a_{E-1}, M) follows the last entry.  Entry
+// j with carry-in c (the g of removed predecessors, gk:80/102) starts at
+// G = g_j + c and walks its gap in order: record i is absorbed iff
+// g_i + G + d_j <= T (G += g_i), else emitted as (v_i, g_i, G + d_j - g_i)
+// (gk:94-99); the entry is then removed (carry G) iff j+1 < E and
+// G + g_{j+1} + d_{j+1} <= T (gk:79/101), else emitted as (v_j, G, d_j).
+// The tail chains records (gk:86-92).  Lane l owns entries [lK, lK+K); the
+// carries are resolved by rounds (each lane re-walks its block from its
+// left neighbour's last carry-out) until no carry-in changes -- lane 0's is
+// fixed, so the fixpoint is the sequential walk.  Then counts, a wave scan
+// and a second walk write the records in order.
+__device__ __forceinline__ void merge_walk(const MergeLDS& m, int E, int M, int64_t T, int outcap, int lane,
+                                           int* sh_out) {
+  int32_t* ga = m.rg;  // a_j (records are in iv/ig/id by now)
+  for (int j = lane; j < E; j += 64) {
+    const double tvj = m.tv[j];
+    int lo = 0, hi = M;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (m.iv[mid] < tvj) lo = mid + 1; else hi = mid;
+    }
+    ga[j] = lo;
+  }
+  __syncthreads();
+  const int K = (E + 63) >> 6;
+  const int j0 = lane * K;
+  const int jend = min(j0 + K, E);
+  // walk of the lane's block from carry-in c; returns the carry-out and
+  // the number of records it emits (out != NULL: also writes them)
+  auto walk = [&](int64_t c, int& cnt_out, int obase, bool write) -> int64_t {
+    int no_l = 0;
+    for (int j = j0; j < jend; ++j) {
+      int64_t G = (int64_t)m.tg[j] + c;
+      const int64_t dj = m.td[j];
+      const int ib = j == 0 ? 0 : ga[j - 1];
+      const int ie = ga[j];
+      for (int i = ib; i < ie; ++i) {
+        const int64_t gi = m.ig[i];
+        if (gi + G + dj <= T) {
+          G += gi;
+        } else {
+          if (write) {
+            m.ov[obase + no_l] = m.iv[i];
+            m.og[obase + no_l] = (int32_t)gi;
+            m.od[obase + no_l] = (int32_t)(G + dj - gi);
+          }
+          ++no_l;
+        }
+      }
+      const bool rem = (j + 1 < E) && (G + m.tg[j + 1] + m.td[j + 1] <= T);
+      if (rem) {
+        c = G;
+      } else {
+        if (write) {
+          m.ov[obase + no_l] = m.tv[j];
+          m.og[obase + no_l] = (int32_t)G;
+          m.od[obase + no_l] = (int32_t)dj;
+        }
+        ++no_l;
+        c = 0;
+      }
+    }
+    cnt_out = no_l;
+    return c;
+  };
+  int64_t cin = 0;
+  int cnt_blk = 0;
+  for (int round = 0; round <= 64; ++round) {
+    const int64_t cout = walk(cin, cnt_blk, 0, false);
+    int64_t ncin = __shfl_up(cout, 1, 64);
+    if (lane == 0) ncin = 0;
+    if (__ballot(ncin != cin) == 0) break;
+    cin = ncin;
+  }
+  // the tail (gk:85-92), on the lane owning the last entry
+  const int tail_lane = E == 0 ? 0 : (E - 1) / K;
+  const int t0 = E == 0 ? 0 : ga[E - 1];
+  int cnt_tail = 0;
+  if (lane == tail_lane) {
+    int64_t acc = 0;
+    for (int i = t0; i < M; ++i) {
+      acc += m.ig[i];
+      if (i + 1 < M && acc + m.ig[i + 1] + m.id[i + 1] <= T) continue;  // into record i+1
+      ++cnt_tail;
+      acc = 0;
+    }
+  }
+  const int mine = (j0 < E ? cnt_blk : 0) + cnt_tail;
+  const uint32_t incl = wave_incl_scan_u32((uint32_t)mine, lane);
+  const int total = __builtin_amdgcn_readlane((int)incl, 63);
+  if (total > outcap) {
+    if (lane == 0) *sh_out = -1;
+  } else {
+    const int obase = (int)incl - mine;
+    int wrote = 0;
+    if (j0 < E) walk(cin, wrote, obase, true);
+    if (lane == tail_lane) {
+      int o = obase + wrote;
+      int64_t acc = 0;
+      for (int i = t0; i < M; ++i) {
+        acc += m.ig[i];
+        if (i + 1 < M && acc + m.ig[i + 1] + m.id[i + 1] <= T) continue;
+        m.ov[o] = m.iv[i];
+        m.og[o] = (int32_t)acc;
+        m.od[o] = m.id[i];
+        ++o;
+        acc = 0;
+      }
+    }
+    if (lane == 0) *sh_out = total;
+  }
+}
+
 template <bool GLOBAL>
 __global__ __launch_bounds__(64) void k_merge(MergeArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -4819,34 +5052,7 @@ __global__ __launch_bounds__(64) void k_merge(MergeArgs a) {
           __syncthreads();
           continue;
         }
-        int base = 0;
-        for (int c0 = 0; c0 < ncand; c0 += 64) {
-          const int c = c0 + lane;
-          int64_t gv = 0;
-          double vv = 0.0;
-          if (c < ncand) {
-            if (c == 0) {
-              gv = (int64_t)otab[0].g + otab[0].d - spread - 1;
-              vv = os.mn[s];
-            } else if (c < oE) {
-              gv = (int64_t)otab[c].g + otab[c].d - otab[c - 1].d;
-              vv = otab[c - 1].v;
-            } else {
-              gv = spread + 1 - otab[oE - 1].d;
-              vv = otab[oE - 1].v;
-            }
-          }
-          const bool keep = (c < ncand) && gv > 0;
-          const unsigned long long bal = __ballot(keep);
-          const int before = __popcll(bal & ((1ull << lane) - 1ull));
-          if (keep) {
-            m.rv[base + before] = vv;
-            m.rg[base + before] = (int32_t)gv;
-            m.rd[base + before] = 0;
-          }
-          base += __popcll(bal);
-        }
-        nrec = base;
+        nrec = merge_convert(m, otab, oE, spread, os.mn[s], lane);
         n += on;  // gk:149
         if (lane == 0) {  // gk:151-152: min()/max() keep self's value on ties
           const double omn = os.mn[s], omx = os.mx[s];
@@ -4874,75 +5080,8 @@ __global__ __launch_bounds__(64) void k_merge(MergeArgs a) {
       __syncthreads();
       continue;
     }
-    // ---- stable order of self's raw pending values (gk:72) ------------------
-    if (p <= GK_MERGE_RANK_MAX) {
-      // few values: each lane ranks its values against all of them
-      for (int i = lane; i < p; i += 64) m.ov[i] = pb[i];
-      __syncthreads();
-      for (int i = lane; i < p; i += 64) {
-        const double x = m.ov[i];
-        int rk = 0;
-        for (int t = 0; t < p; ++t) {
-          const double y = m.ov[t];
-          rk += (y < x) || (y == x && t < i);
-        }
-        m.sp[rk] = x;
-      }
-    } else {
-      // a large flush period (eps < 1/256): bitonic sort of (value, index)
-      // in the output arrays (free here; cap >= pow2 above p for every class)
-      int N = 1;
-      while (N < p) N <<= 1;
-      for (int i = lane; i < N; i += 64) {
-        m.ov[i] = i < p ? pb[i] : __longlong_as_double(0x7ff0000000000000LL);
-        m.og[i] = i < p ? i : INT32_MAX;
-      }
-      __syncthreads();
-      for (int k = 2; k <= N; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-          for (int pp = lane; pp < N / 2; pp += 64) {
-            const int i = ((pp & ~(j - 1)) << 1) | (pp & (j - 1));
-            const int l = i + j;
-            const double a = m.ov[i], b = m.ov[l];
-            const int ia = m.og[i], ib = m.og[l];
-            const bool a_gt = (a > b) || (a == b && ia > ib);
-            if (a_gt == ((i & k) == 0)) {
-              m.ov[i] = b;
-              m.ov[l] = a;
-              m.og[i] = ib;
-              m.og[l] = ia;
-            }
-          }
-          __syncthreads();
-        }
-      }
-      for (int i = lane; i < p; i += 64) m.sp[i] = m.ov[i];
-    }
-    __syncthreads();
-    // ---- merged incoming list: `self.incoming + entries` sorted stably, so on
-    //      equal values the raw pending values come first (gk:71-72) ----------
-    for (int r = lane; r < p; r += 64) {
-      const double x = m.sp[r];
-      int lo = 0, hi = nrec;  // records strictly below x
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (m.rv[mid] < x) lo = mid + 1; else hi = mid;
-      }
-      m.iv[r + lo] = x;
-      m.ig[r + lo] = 1;
-      m.id[r + lo] = 0;
-    }
-    for (int t = lane; t < nrec; t += 64) {
-      const double y = m.rv[t];
-      int lo = 0, hi = p;  // pending values <= y
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (m.sp[mid] <= y) lo = mid + 1; else hi = mid;
-      }
-      m.iv[t + lo] = y;
-      m.ig[t + lo] = m.rg[t];
-      m.id[t + lo] = m.rd[t];
-    }
+    merge_sort_pending(m, pb, p, lane);
+    merge_incoming(m, p, nrec, lane);
     for (int j = lane; j < E; j += 64) {
       const GKRec rc = tab[j];
       m.tv[j] = rc.v;
@@ -4950,122 +5089,7 @@ __global__ __launch_bounds__(64) void k_merge(MergeArgs a) {
       m.td[j] = rc.d;
     }
     __syncthreads();
-    // ---- the four-rule walk of gk:76-106, wave-parallel ----------------------
-    // Incoming records (sorted) fall into gaps: record i precedes entry j iff
-    // iv[i] < tv[j] (gk:93), so gap j holds [a_{j-1}, a_j) with a_j = #{i :
-    // iv[i] < tv[j]}, and the tail [a_{E-1}, M) follows the last entry.  Entry
-    // j with carry-in c (the g of removed predecessors, gk:80/102) starts at
-    // G = g_j + c and walks its gap in order: record i is absorbed iff
-    // g_i + G + d_j <= T (G += g_i), else emitted as (v_i, g_i, G + d_j - g_i)
-    // (gk:94-99); the entry is then removed (carry G) iff j+1 < E and
-    // G + g_{j+1} + d_{j+1} <= T (gk:79/101), else emitted as (v_j, G, d_j).
-    // The tail chains records (gk:86-92).  Lane l owns entries [lK, lK+K); the
-    // carries are resolved by rounds (each lane re-walks its block from its
-    // left neighbour's last carry-out) until no carry-in changes -- lane 0's is
-    // fixed, so the fixpoint is the sequential walk.  Then counts, a wave scan
-    // and a second walk write the records in order.
-    {
-      const int64_t T = (int64_t)floor(st.two_eps * (double)(n - 1));  // gk:70
-      const int M = p + nrec;
-      int32_t* ga = m.rg;  // a_j (records are in iv/ig/id by now)
-      for (int j = lane; j < E; j += 64) {
-        const double tvj = m.tv[j];
-        int lo = 0, hi = M;
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (m.iv[mid] < tvj) lo = mid + 1; else hi = mid;
-        }
-        ga[j] = lo;
-      }
-      __syncthreads();
-      const int K = (E + 63) >> 6;
-      const int j0 = lane * K;
-      const int jend = min(j0 + K, E);
-      // walk of the lane's block from carry-in c; returns the carry-out and
-      // the number of records it emits (out != NULL: also writes them)
-      auto walk = [&](int64_t c, int& cnt_out, int obase, bool write) -> int64_t {
-        int no_l = 0;
-        for (int j = j0; j < jend; ++j) {
-          int64_t G = (int64_t)m.tg[j] + c;
-          const int64_t dj = m.td[j];
-          const int ib = j == 0 ? 0 : ga[j - 1];
-          const int ie = ga[j];
-          for (int i = ib; i < ie; ++i) {
-            const int64_t gi = m.ig[i];
-            if (gi + G + dj <= T) {
-              G += gi;
-            } else {
-              if (write) {
-                m.ov[obase + no_l] = m.iv[i];
-                m.og[obase + no_l] = (int32_t)gi;
-                m.od[obase + no_l] = (int32_t)(G + dj - gi);
-              }
-              ++no_l;
-            }
-          }
-          const bool rem = (j + 1 < E) && (G + m.tg[j + 1] + m.td[j + 1] <= T);
-          if (rem) {
-            c = G;
-          } else {
-            if (write) {
-              m.ov[obase + no_l] = m.tv[j];
-              m.og[obase + no_l] = (int32_t)G;
-              m.od[obase + no_l] = (int32_t)dj;
-            }
-            ++no_l;
-            c = 0;
-          }
-        }
-        cnt_out = no_l;
-        return c;
-      };
-      int64_t cin = 0;
-      int cnt_blk = 0;
-      for (int round = 0; round <= 64; ++round) {
-        const int64_t cout = walk(cin, cnt_blk, 0, false);
-        int64_t ncin = __shfl_up(cout, 1, 64);
-        if (lane == 0) ncin = 0;
-        if (__ballot(ncin != cin) == 0) break;
-        cin = ncin;
-      }
-      // the tail (gk:85-92), on the lane owning the last entry
-      const int tail_lane = E == 0 ? 0 : (E - 1) / K;
-      const int t0 = E == 0 ? 0 : ga[E - 1];
-      int cnt_tail = 0;
-      if (lane == tail_lane) {
-        int64_t acc = 0;
-        for (int i = t0; i < M; ++i) {
-          acc += m.ig[i];
-          if (i + 1 < M && acc + m.ig[i + 1] + m.id[i + 1] <= T) continue;  // into record i+1
-          ++cnt_tail;
-          acc = 0;
-        }
-      }
-      const int mine = (j0 < E ? cnt_blk : 0) + cnt_tail;
-      const uint32_t incl = wave_incl_scan_u32((uint32_t)mine, lane);
-      const int total = __builtin_amdgcn_readlane((int)incl, 63);
-      if (total > outcap) {
-        if (lane == 0) sh_out = -1;
-      } else {
-        const int obase = (int)incl - mine;
-        int wrote = 0;
-        if (j0 < E) walk(cin, wrote, obase, true);
-        if (lane == tail_lane) {
-          int o = obase + wrote;
-          int64_t acc = 0;
-          for (int i = t0; i < M; ++i) {
-            acc += m.ig[i];
-            if (i + 1 < M && acc + m.ig[i + 1] + m.id[i + 1] <= T) continue;
-            m.ov[o] = m.iv[i];
-            m.og[o] = (int32_t)acc;
-            m.od[o] = m.id[i];
-            ++o;
-            acc = 0;
-          }
-        }
-        if (lane == 0) sh_out = total;
-      }
-    }
+    merge_walk(m, E, p + nrec, (int64_t)floor(st.two_eps * (double)(n - 1)) /* gk:70 */, outcap, lane, &sh_out);
     __syncthreads();
     const int no = sh_out;
     if (no < 0) {
@@ -5087,6 +5111,206 @@ __global__ __launch_bounds__(64) void k_merge(MergeArgs a) {
     }
     __syncthreads();
   }
+}
+
+// ===========================================================================
+// k_rollup: the group-by fold  dst[j].merge(src[members[k]])  for k in
+// [goffs[j], goffs[j+1])  (gk:111-154 per member), one wave per destination.
+// The destination's table is loaded into the carve once and stays there: each
+// member is converted (gk:136-147), merged with the destination's pending
+// values (first merge only, gk:71-72) and walked (gk:76-106) by k_merge's
+// steps, and the walk's output arrays become the table arrays of the next
+// member by a pointer swap.  Table and header go back to global memory once,
+// after the last member.  Members have been flushed by the caller (gk:126 /
+// gk:137; a member with n == 0 is not: gk:121-123).
+// A member whose merge does not fit this launch's capacity level ends the
+// fold there: the state after the member before it is committed (table, n,
+// _min, _max together, so nothing of the failed member is applied twice), its
+// position goes to progress[j] and j to the overflow list; the host raises
+// j's class and re-launches on the list with resume = 1.
+// ===========================================================================
+struct RollupArgs {
+  GKState dst;
+  GKState src;
+  const int64_t* goffs;    // [G + 1]
+  const int64_t* members;  // [goffs[G]] streams of src, each at most once
+  int64_t* progress;       // [G] position of the first member not yet merged (listed destinations)
+  int resume;              // 0: start at goffs[j]; 1: at progress[j]
+  int cap;
+  const int32_t* list;     // destinations to process (NULL = all)
+  int64_t count;
+  int32_t* ovf_count;
+  int32_t* ovf_list;
+  unsigned char* ws;       // global workspace (classes beyond LDS), NULL = dynamic LDS
+  size_t ws_bytes;         // per block
+};
+
+template <bool GLOBAL>
+__global__ __launch_bounds__(64) void k_rollup(RollupArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ int sh_out;
+  const int lane = threadIdx.x;
+  const int CAPL = a.cap;
+  unsigned char* base = GLOBAL ? a.ws + (size_t)blockIdx.x * a.ws_bytes : smem;
+  const MergeLDS m0 = merge_carve(base, CAPL, a.dst.pmax);
+  const GKState& st = a.dst;
+  const GKState& os = a.src;
+  for (int64_t w = blockIdx.x; w < a.count; w += gridDim.x) {
+    const int64_t j = a.list ? (int64_t)a.list[w] : w;
+    const int64_t kend = a.goffs[j + 1];
+    int64_t k = a.resume ? a.progress[j] : a.goffs[j];
+    if (k >= kend) continue;  // an empty group: the destination is not touched (not flushed)
+    GKRec* __restrict__ tab = gk_table_ptr(st, j);
+    const int outcap = min(st.cap[st.cls[j]], CAPL) - 1;  // k_ingest keeps one slot for padding
+    const double* __restrict__ pb = st.pbuf + j * (int64_t)st.pmax;
+    int64_t n = st.n[j];
+    int E = st.E[j];
+    int p = st.pend[j];
+    double mn = st.mn[j], mx = st.mx[j], sum = st.sum[j], avg = st.avg[j];
+    MergeLDS m = m0;
+    if (E > CAPL) {  // the table itself needs a larger level: nothing done yet
+      if (lane == 0) a.progress[j] = k;
+      flag_overflow(a.ovf_count, a.ovf_list, j, lane);
+      __syncthreads();
+      continue;
+    }
+    for (int i = lane; i < E; i += 64) {
+      const GKRec rc = tab[i];
+      m.tv[i] = rc.v;
+      m.tg[i] = rc.g;
+      m.td[i] = rc.d;
+    }
+    __syncthreads();
+    bool ovf = false;
+    // the next member's id, n and table size are loaded one member ahead (no
+    // merge of this fold writes src), off the chain of dependent steps
+    int64_t ms_nx = a.members[k];
+    int64_t on_nx = os.n[ms_nx];
+    int oE_nx = os.E[ms_nx];
+    for (; k < kend; ++k) {
+      const int64_t ms = ms_nx;
+      const int64_t on = on_nx;
+      const int oE = oE_nx;
+      if (k + 1 < kend) {
+        ms_nx = a.members[k + 1];
+        on_nx = os.n[ms_nx];
+        oE_nx = os.E[ms_nx];
+      }
+      const GKRec* __restrict__ otab = gk_table_ptr(os, ms);
+      if (on != 0 && n == 0) {  // gk:125-133: take a copy of (flushed) other; E == p == 0 here
+        if (oE > outcap) {
+          ovf = true;
+          break;
+        }
+        for (int i = lane; i < oE; i += 64) {
+          const GKRec rc = otab[i];
+          m.tv[i] = rc.v;
+          m.tg[i] = rc.g;
+          m.td[i] = rc.d;
+        }
+        n = on;
+        E = oE;
+        p = 0;
+        mn = os.mn[ms];
+        mx = os.mx[ms];
+        sum = os.sum[ms];
+        avg = os.avg[ms];
+        __syncthreads();
+        continue;
+      }
+      int nrec = 0;
+      int64_t n2 = n;
+      double mn2 = mn, mx2 = mx;
+      if (on != 0) {
+        if (oE > CAPL) {  // (oE + 1 candidate records, rv holds CAPL + 1)
+          ovf = true;
+          break;
+        }
+        const int64_t spread = (int64_t)(os.eps * (double)(on - 1));  // gk:136
+        const double omn = os.mn[ms], omx = os.mx[ms];
+        nrec = merge_convert(m, otab, oE, spread, omn, lane);
+        n2 = n + on;  // gk:149
+        if (omn < mn2) mn2 = omn;  // gk:151-152: min()/max() keep self's value on ties
+        if (omx > mx2) mx2 = omx;
+      }
+      // on == 0: gk:121-123, self.merge_compress() with no records
+      if (!gk_count_ok(st, n2)) {
+        ovf = true;
+        break;
+      }
+      merge_sort_pending(m, pb, p, lane);
+      merge_incoming(m, p, nrec, lane);
+      __syncthreads();
+      merge_walk(m, E, p + nrec, (int64_t)floor(st.two_eps * (double)(n2 - 1)) /* gk:70 */, outcap, lane, &sh_out);
+      __syncthreads();
+      const int no = sh_out;
+      if (no < 0) {
+        ovf = true;
+        break;
+      }
+      // the output is the next member's table
+      { double* t = m.tv; m.tv = m.ov; m.ov = t; }
+      { int32_t* t = m.tg; m.tg = m.og; m.og = t; }
+      { int32_t* t = m.td; m.td = m.od; m.od = t; }
+      E = no;
+      n = n2;
+      p = 0;
+      mn = mn2;
+      mx = mx2;
+    }
+    // commit: the fold up to (not including) member k
+    for (int i = lane; i < E; i += 64) {
+      GKRec rc;
+      rc.v = m.tv[i];
+      rc.g = m.tg[i];
+      rc.d = m.td[i];
+      tab[i] = rc;
+    }
+    if (lane == 0) {
+      st.n[j] = n;
+      st.E[j] = E;
+      st.pend[j] = p;
+      st.mn[j] = mn;
+      st.mx[j] = mx;
+      st.sum[j] = sum;
+      st.avg[j] = avg;
+      if (ovf) a.progress[j] = k;
+    }
+    if (ovf) flag_overflow(a.ovf_count, a.ovf_list, j, lane);
+    __syncthreads();
+  }
+}
+
+// Roll-up argument checks, before anything is mutated.  bad bit 0: the
+// offsets do not start at 0 or decrease; bit 1: a member outside [0, S);
+// bit 2: a source stream listed more than once (bitmap: one bit per source
+// stream, zeroed by the caller).
+__global__ void k_rollup_check_offsets(const int64_t* __restrict__ goffs, int64_t G, int32_t* __restrict__ bad) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j == 0 && goffs[0] != 0) atomicOr(bad, 1);
+  if (j < G && goffs[j + 1] < goffs[j]) atomicOr(bad, 1);
+}
+
+__global__ void k_rollup_check_members(const int64_t* __restrict__ members, int64_t M, int64_t S,
+                                       uint32_t* __restrict__ bitmap, int32_t* __restrict__ bad) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= M) return;
+  const int64_t ms = members[k];
+  if (ms < 0 || ms >= S) {
+    atomicOr(bad, 2);
+    return;
+  }
+  const uint32_t bit = 1u << (ms & 31);
+  if (atomicOr(&bitmap[ms >> 5], bit) & bit) atomicOr(bad, 4);
+}
+
+// the members that the reference flushes (gk:126 / gk:137: every `other` with n != 0)
+__global__ void k_rollup_flush_list(GKState src, const int64_t* __restrict__ members, int64_t M,
+                                    int32_t* __restrict__ count, int32_t* __restrict__ list) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= M) return;
+  const int64_t ms = members[k];
+  if (src.n[ms] != 0) list[atomicAdd(count, 1)] = (int32_t)ms;
 }
 
 // ===========================================================================
@@ -5640,6 +5864,66 @@ hipError_t gk_launch_merge(const MergeArgsHost& h, hipStream_t stream) {
   int64_t grid = (int64_t)num_cu() * 8;
   if (grid > h.count) grid = h.count;
   hipLaunchKernelGGL(k_merge<false>, dim3((unsigned)grid), dim3(64), lds, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t gk_launch_rollup(const RollupArgsHost& h, hipStream_t stream) {
+  if (h.count <= 0) return hipSuccess;
+  RollupArgs a;
+  a.dst = h.dst;
+  a.src = h.src;
+  a.goffs = h.goffs;
+  a.members = h.members;
+  a.progress = h.progress;
+  a.resume = h.resume;
+  a.cap = h.cap;
+  a.list = h.list;
+  a.count = h.count;
+  a.ovf_count = h.ovf_count;
+  a.ovf_list = h.ovf_list;
+  a.ws = h.ws;
+  a.ws_bytes = h.ws_bytes;
+  // (k_merge's carve: the fold swaps its table and output arrays, no array more)
+  const size_t lds = gk_merge_lds_bytes(h.cap, h.dst.pmax);
+  if (h.ws) {
+    if (h.ws_bytes < lds || h.ws_blocks <= 0) return hipErrorInvalidValue;
+    int64_t grid = h.ws_blocks;
+    if (grid > h.count) grid = h.count;
+    hipLaunchKernelGGL(k_rollup<true>, dim3((unsigned)grid), dim3(64), 0, stream, a);
+    return hipGetLastError();
+  }
+  if (lds > 160 * 1024 - 64) return hipErrorInvalidValue;
+  if (lds > 48 * 1024)
+    (void)hipFuncSetAttribute((const void*)k_rollup<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  // one block per destination (up to 2^20; the kernel's loop takes the rest):
+  // a fold is a long chain of dependent steps, so every wave the LDS carve
+  // lets a CU hold should be resident, and folds of uneven length are handed
+  // out as blocks retire
+  int64_t grid = (int64_t)1 << 20;
+  if (grid > h.count) grid = h.count;
+  hipLaunchKernelGGL(k_rollup<false>, dim3((unsigned)grid), dim3(64), lds, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t gk_launch_rollup_check_offsets(const int64_t* goffs, int64_t G, int32_t* bad, hipStream_t stream) {
+  const int64_t nthr = G > 0 ? G : 1;  // (thread 0 checks goffs[0] also when there is no group)
+  hipLaunchKernelGGL(k_rollup_check_offsets, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, goffs, G, bad);
+  return hipGetLastError();
+}
+
+hipError_t gk_launch_rollup_check_members(const int64_t* members, int64_t M, int64_t S, uint32_t* bitmap, int32_t* bad,
+                                          hipStream_t stream) {
+  if (M <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_rollup_check_members, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, stream, members, M, S,
+                     bitmap, bad);
+  return hipGetLastError();
+}
+
+hipError_t gk_launch_rollup_flush_list(const GKState& src, const int64_t* members, int64_t M, int32_t* count,
+                                       int32_t* list, hipStream_t stream) {
+  if (M <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_rollup_flush_list, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, stream, src, members, M,
+                     count, list);
   return hipGetLastError();
 }
 

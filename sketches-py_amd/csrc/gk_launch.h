@@ -158,6 +158,38 @@ hipError_t gk_launch_query_list(const GKState& st, const int32_t* list, const in
                                 bool qfix, hipStream_t stream);
 size_t gk_merge_lds_bytes(int cap, int pmax);
 hipError_t gk_launch_merge(const MergeArgsHost& h, hipStream_t stream);
+// k_rollup: the fold dst[j].merge(src[members[k]]), k in [goffs[j], goffs[j+1]),
+// one wave per destination with its table on chip across the members.  cap /
+// list / count / ovf_* / ws* as MergeArgsHost (the workspace is k_merge's).  A
+// destination that outgrows `cap` commits the fold before the member that did
+// not fit, records that member's position in progress[j] and joins the
+// overflow list; resume = 1 starts each listed destination at progress[j].
+struct RollupArgsHost {
+  GKState dst;
+  GKState src;             // its members already flushed (gk:126 / gk:137)
+  const int64_t* goffs;    // device [G + 1]
+  const int64_t* members;  // device [goffs[G]]
+  int64_t* progress;       // device [G]
+  int resume;
+  int cap;
+  const int32_t* list;
+  int64_t count;
+  int32_t* ovf_count;
+  int32_t* ovf_list;
+  unsigned char* ws;
+  size_t ws_bytes;
+  int64_t ws_blocks;
+};
+hipError_t gk_launch_rollup(const RollupArgsHost& h, hipStream_t stream);
+// roll-up argument checks into *bad (zeroed by the caller): bit 0 offsets not
+// starting at 0 or decreasing, bit 1 a member outside [0, S), bit 2 a source
+// stream listed twice (bitmap: (S + 31) / 32 zeroed words)
+hipError_t gk_launch_rollup_check_offsets(const int64_t* goffs, int64_t G, int32_t* bad, hipStream_t stream);
+hipError_t gk_launch_rollup_check_members(const int64_t* members, int64_t M, int64_t S, uint32_t* bitmap, int32_t* bad,
+                                          hipStream_t stream);
+// the members with n != 0 (those the reference flushes) into list, *count of them (zeroed by the caller)
+hipError_t gk_launch_rollup_flush_list(const GKState& src, const int64_t* members, int64_t M, int32_t* count,
+                                       int32_t* list, hipStream_t stream);
 // every stream back to an empty sketch in class 0; ctr: also zero the set's
 // counter words [0, GK_CTR_FATAL) (slots used, member-list lengths) and the
 // per-call block [GK_CTR_CALL, GK_CALL_BYTES) (what begin_call's memset zeroes)

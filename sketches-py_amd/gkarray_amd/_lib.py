@@ -59,6 +59,7 @@ SYMBOLS = {
     "gk_ingest_quantiles": (_INT, [_P, _P, _P, ctypes.POINTER(_D), _INT, _P, _INT, _P]),
     "gk_stats": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gk_merge": (_INT, [_P, ctypes.POINTER(_P), _INT, _P]),
+    "gk_rollup": (_INT, [_P, _P, _P, _P, _P]),
     "gk_merge_compress": (_INT, [_P, _P, _P, _P, _P, _P]),
     "gk_export_sizes": (_INT, [_P, _P, _P]),
     "gk_export": (_INT, [_P, _P, _P, _P, _P, _P]),

@@ -385,6 +385,66 @@ class StreamSet:
             raise UnequalEpsilonException("Cannot merge two GKArrays with different epsilon values")
         self._check(rc)
 
+    # ---------------------------------------------------------------- roll-up
+    def rollup_from(self, src, group_offsets, members):
+        """Group-by roll-up (``gk_rollup``): for every stream j of this set, in
+        order of k, ``self[j].merge(src[members[k]])`` for k in
+        ``group_offsets[j] .. group_offsets[j+1]-1`` (gk:111-154).
+
+        ``src`` is another set with the same eps (any stream count);
+        ``group_offsets`` is int64[num_streams+1] starting at 0, non-decreasing;
+        ``members`` are indices into ``src``, each at most once.  This set keeps
+        its state from before the call, so a roll-up can be continued by a
+        later call; a stream with an empty group is not touched.  Members are
+        flushed (mutated) as the reference flushes ``other``; every other
+        stream of ``src`` is left as it is."""
+        if not isinstance(src, StreamSet):
+            raise ValueError("src must be a StreamSet")
+        if src.eps != self.eps:
+            from .gkarray import UnequalEpsilonException
+            raise UnequalEpsilonException("Cannot merge two GKArrays with different epsilon values")
+        if src.is_cpu != self.is_cpu:
+            raise ValueError("cannot roll up a CPU-engine set into a GPU-engine set or back "
+                             "(export / import the state)")
+        if not self.is_cpu and src.device != self.device:
+            raise ValueError("both sets must live on one device")
+        go = self._dev(group_offsets, torch.int64)
+        mem = self._dev(members, torch.int64)
+        if go.dim() != 1 or go.numel() != self.num_streams + 1:
+            raise ValueError("group_offsets must have num_streams+1 entries")
+        if mem.dim() != 1:
+            raise ValueError("members must be one-dimensional")
+        if mem.numel() == 0:
+            mem = torch.zeros(1, dtype=torch.int64, device=self.device)
+        with self._ctx():
+            rc = self._lib.gk_rollup(self._h, src._h, _ptr(go), _ptr(mem), self._sp())
+        if rc == L.GK_E_EPS_MISMATCH:
+            from .gkarray import UnequalEpsilonException
+            raise UnequalEpsilonException("Cannot merge two GKArrays with different epsilon values")
+        self._check(rc)
+
+    def rollup_by_key(self, src, keys):
+        """Roll-up by destination key: ``keys`` is int64[src.num_streams],
+        ``keys[s]`` the stream of this set that source stream s is merged into,
+        -1 for "not rolled up".  The members of a group are taken in ascending
+        source index."""
+        if not isinstance(src, StreamSet):
+            raise ValueError("src must be a StreamSet")
+        k = self._dev(keys, torch.int64)
+        if k.dim() != 1 or k.numel() != src.num_streams:
+            raise ValueError("keys must have one entry per source stream")
+        G = self.num_streams
+        if k.numel() and (int(k.max().item()) >= G or int(k.min().item()) < -1):
+            raise ValueError("keys must lie in [-1, num_streams)")
+        # CSR by a stable sort: equal keys keep ascending source index
+        sk, order = torch.sort(k, stable=True)
+        members = order[sk >= 0]
+        counts = torch.bincount(sk[sk >= 0], minlength=G) if G else torch.zeros(0, dtype=torch.int64, device=k.device)
+        go = torch.zeros(G + 1, dtype=torch.int64, device=k.device)
+        if G:
+            go[1:] = torch.cumsum(counts, 0)
+        self.rollup_from(src, go, members)
+
     # ---- packed state (gk_pack_bytes / gk_pack / gk_fold_packed) -------------
     def pack_bytes(self):
         """Size of this set's packed state (one contiguous buffer: header
