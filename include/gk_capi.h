@@ -97,8 +97,54 @@ int gk_reset(gk_set* set, void* stream);
 int gk_ingest(gk_set* set, const double* values, const int64_t* offsets,
               void* stream);
 
+/* Keyed ingest: samples in arrival order, (ids[i], values[i]) for i in
+ * [0, count), instead of a CSR batch.
+ *
+ * gk_group_by_key is the stable group-by of the samples into a CSR batch over
+ * the set's S streams; gk_ingest_keyed is
+ *     for i in [0, count): stream ids[i] .add(values[i])        (gk:49-61)
+ * and then, nq > 0, quantiles(qs) of every stream as gk_ingest_quantiles does.
+ *  - Memory and sizes.  `ids` (int32), `values` (float64), `out_values` (room
+ *    for `count` doubles) and `out_offsets` (int64[S+1]) are device memory for
+ *    the GPU engine, host memory for the CPU engine.  0 <= count <= 2^31-1,
+ *    anything else is GK_E_ARG.  count == 0 is valid (an ingest of an empty
+ *    batch; with nq > 0 exactly gk_quantiles), and `ids`, `values` and
+ *    `out_values` may then be NULL.
+ *  - Grouping rule.  Stream s receives the values whose id is s in ascending
+ *    sample index (the grouping is a STABLE sort by id).  Values are copied
+ *    bit for bit (-0.0, NaN payloads, infinities, denormals).
+ *    out_offsets[s+1] - out_offsets[s] is the number of samples with id s,
+ *    out_offsets[0] == 0; out_values[0 .. out_offsets[S]) is written.
+ *  - Negative ids are skipped ("not for this set").
+ *  - An id >= S is an error.  The GPU engine finds it on the device and reports
+ *    it as it reports GK_E_OVERFLOW: GK_E_ARG from a later call on the set, at
+ *    the latest from gk_sync, with the first bad sample index and its id in
+ *    the message (the host engine returns GK_E_ARG from the call itself).  The
+ *    call then adds no value to any stream: gk_group_by_key leaves out_offsets
+ *    all zero, and a query fused into gk_ingest_keyed answers as gk_quantiles
+ *    would from the pre-call state (which flushes pending values).
+ *  - Both calls only enqueue, as gk_ingest does.  The caller keeps `ids`,
+ *    `values` and the outputs alive and unchanged until the set's next call or
+ *    gk_sync.  A call that has to grow the set's grouping scratch synchronises
+ *    first; GK_E_NOMEM is returned before anything is mutated.
+ *  - gk_ingest_keyed is gk_group_by_key into buffers the set owns, followed by
+ *    exactly gk_ingest (nq == 0) or gk_ingest_quantiles on those buffers; qs,
+ *    nq, out and mode are checked as gk_ingest_quantiles checks them.  S == 0
+ *    returns GK_OK.
+ *  - Scratch (GPU engine; owned by the set, only grows, freed by gk_destroy):
+ *    two (int32 id, float64 value) pair buffers of `count` entries, 24 bytes
+ *    per sample (S > 65536, three or more radix passes; 16 bytes for
+ *    256 < S <= 65536, 4 bytes for S <= 256), 0.25 byte per sample of
+ *    per-workgroup digit counts, and for gk_ingest_keyed the grouped batch:
+ *    8 bytes per sample + 8 (S+1) bytes. */
+int gk_group_by_key(gk_set* set, const int32_t* ids, const double* values, int64_t count,
+                    double* out_values, int64_t* out_offsets, void* stream);
+int gk_ingest_keyed(gk_set* set, const int32_t* ids, const double* values, int64_t count,
+                    const double* qs, int nq, double* out, int mode, void* stream);
+
 /* Wait for the set's work on `stream`; return (and clear) an asynchronous
- * error of an earlier call (GK_E_OVERFLOW, see Conventions) or GK_OK. */
+ * error of an earlier call (GK_E_OVERFLOW, see Conventions; GK_E_ARG for an
+ * id >= S of a keyed call) or GK_OK. */
 int gk_sync(gk_set* set, void* stream);
 
 /* GKArray.merge_compress() with no argument (gk:63-109) on every stream that

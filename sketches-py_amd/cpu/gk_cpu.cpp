@@ -113,6 +113,9 @@ struct gk_set {
   double ingest_ms = 0;
   int64_t launches = 0;
   gk_set* fold_scratch = nullptr;  // gk_fold_packed (made on first use)
+  // gk_ingest_keyed: the grouped batch (only grows)
+  std::vector<double> key_vals;
+  std::vector<int64_t> key_offs;
 };
 
 namespace {
@@ -496,6 +499,63 @@ int gk_ingest(gk_set* h, const double* values, const int64_t* offsets, void* str
   int rc = check_set(h);
   if (rc) return rc;
   return ingest_impl(h, values, offsets, nullptr, 0, nullptr, GK_Q_LIST);
+}
+
+// Stable group-by of (id, value) samples by a counting sort: histogram, scan,
+// in-order scatter.  A bad id (>= S) leaves out_offsets all zero.
+static int group_impl(const gk_set* h, const int32_t* ids, const double* values, int64_t count, double* out_values,
+                      int64_t* out_offsets) {
+  if (count < 0 || count > INT32_MAX) return fail(GK_E_ARG, "count %lld outside [0, 2^31-1]", (long long)count);
+  if (!out_offsets) return fail(GK_E_ARG, "out_offsets is null");
+  if (count > 0 && (!ids || !values || !out_values)) return fail(GK_E_ARG, "ids, values or out_values is null");
+  const int64_t S = h->S;
+  std::fill(out_offsets, out_offsets + S + 1, (int64_t)0);
+  for (int64_t i = 0; i < count; ++i) {
+    const int64_t id = ids[i];
+    if (id < 0) continue;  // "not for this set"
+    if (id >= S) {
+      std::fill(out_offsets, out_offsets + S + 1, (int64_t)0);
+      return fail(GK_E_ARG, "sample %lld has stream id %lld outside [0, %lld)", (long long)i, (long long)id,
+                  (long long)S);
+    }
+    ++out_offsets[id + 1];
+  }
+  for (int64_t s = 0; s < S; ++s) out_offsets[s + 1] += out_offsets[s];
+  // out_offsets[s] is the next free position of stream s while scattering,
+  // and ends as the start of stream s + 1: shifted back afterwards
+  for (int64_t i = 0; i < count; ++i)
+    if (ids[i] >= 0) out_values[out_offsets[ids[i]]++] = values[i];
+  for (int64_t s = S; s > 0; --s) out_offsets[s] = out_offsets[s - 1];
+  out_offsets[0] = 0;
+  return GK_OK;
+}
+
+int gk_group_by_key(gk_set* h, const int32_t* ids, const double* values, int64_t count, double* out_values,
+                    int64_t* out_offsets, void* stream) {
+  (void)stream;
+  int rc = check_set(h);
+  if (rc) return rc;
+  return group_impl(h, ids, values, count, out_values, out_offsets);
+}
+
+int gk_ingest_keyed(gk_set* h, const int32_t* ids, const double* values, int64_t count, const double* qs, int nq,
+                    double* out, int mode, void* stream) {
+  int rc = check_set(h);
+  if (!rc) rc = check_query(qs, nq, out, mode);
+  if (rc) return rc;
+  if (count < 0 || count > INT32_MAX) return fail(GK_E_ARG, "count %lld outside [0, 2^31-1]", (long long)count);
+  if (h->S == 0) return GK_OK;
+  try {
+    if ((int64_t)h->key_vals.size() < std::max<int64_t>(count, 1)) h->key_vals.resize((size_t)std::max<int64_t>(count, 1));
+    h->key_offs.resize((size_t)h->S + 1);
+  } catch (...) {
+    return fail(GK_E_NOMEM, "grouped batch of %lld samples failed", (long long)count);
+  }
+  // a bad id is returned here: nothing has been mutated
+  rc = group_impl(h, ids, values, count, h->key_vals.data(), h->key_offs.data());
+  if (rc) return rc;
+  if (nq == 0) return gk_ingest(h, h->key_vals.data(), h->key_offs.data(), stream);
+  return gk_ingest_quantiles(h, h->key_vals.data(), h->key_offs.data(), qs, nq, out, mode, stream);
 }
 
 int gk_flush(gk_set* h, void* stream) {

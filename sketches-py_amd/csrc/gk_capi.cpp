@@ -148,6 +148,22 @@ struct gk_set {
   gk_set* fold_scratch = nullptr;
   gk_set* self_scratch = nullptr;  // snapshot source of dst.merge(dst), only during that merge
   int64_t* d_roll_prog = nullptr;  // gk_rollup into this set: the member a resumed fold starts at (first use)
+  // Keyed ingest (gk_group_by_key / gk_ingest_keyed; all made on first use,
+  // only grown, freed in gk_destroy): the grouping scratch, the grouped batch
+  // gk_ingest_keyed ingests from -- h->last.x / h->last.offs of such a call,
+  // so the next call's grouping is enqueued only after its settle -- and the
+  // pinned copy of the cumulative bad-id block (kg.cum), read back with the
+  // counters before ev_done.
+  GKGroupScratch kg;
+  int64_t kg_cap = 0;       // samples the pair buffers hold
+  int kg_pairs = 0;         // id buffers allocated (1 or 2; one value buffer fewer)
+  int64_t kg_tiles = 0;     // tiles kg.hist holds
+  int64_t kg_sums = 0;      // entries of kg.sums
+  double* kg_vals = nullptr;  // grouped values (kg_vals_cap doubles) and offsets (S + 1)
+  int64_t kg_vals_cap = 0;
+  int64_t* kg_offs = nullptr;
+  unsigned long long* h_kg = nullptr;  // pinned GK_KG_CUM_WORDS words
+  unsigned long long kg_bad_seen = 0;  // voided keyed calls already reported
   // Host-walked chains: the gk:52-59 chains of the
   // longest streams run on host cores beside the GPU ingest.  hc_min: shortest
   // stream taken (0: off; GK_HOST_CHAINS=0 / GK_HOST_CHAIN_MIN); hc_threads:
@@ -333,6 +349,18 @@ void poll(gk_set* h, bool block) {
     h->sticky_msg = buf;
   }
   h->fatal_seen = fatal;
+  // a keyed call that met an id >= S (it added nothing): reported the same way
+  if (h->h_kg && h->h_kg[0] > h->kg_bad_seen) {
+    if (h->sticky == GK_OK) {
+      char buf[256];
+      snprintf(buf, sizeof(buf),
+               "keyed ingest: sample %lld has stream id %lld outside [0, %lld): no value of that call was added",
+               (long long)h->h_kg[1], (long long)h->h_kg[2], (long long)h->S);
+      h->sticky = GK_E_ARG;
+      h->sticky_msg = buf;
+    }
+    h->kg_bad_seen = h->h_kg[0];
+  }
 }
 
 int promote_rounds(gk_set* h, const double* x, const int64_t* offs, int force, const GKQuery& q, hipStream_t s,
@@ -492,6 +520,8 @@ int mark_done(gk_set* h, hipStream_t s, bool ingest) {
                          hipMemcpyDeviceToHost, s));
   if (h->ps.wg_count && h->wg_trace)
     HIP_TRY(hipMemcpyAsync(h->h_ctr + GK_CTR_WORDS, h->ps.wg_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  if (h->kg.cum)
+    HIP_TRY(hipMemcpyAsync(h->h_kg, h->kg.cum, GK_KG_CUM_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipEventRecord(h->ev_done, s));
   h->done_pending = true;
   h->void_defer = false;  // (the readback in flight is now this call's)
@@ -1414,7 +1444,9 @@ int gk_destroy(gk_set* h) {
                   st.avg,     st.cls,        st.slot,        st.pbuf,        h->d_qs,
                   h->d_ctr,   h->d_zero_offs, h->d_long_list, h->d_long_n,
                   h->ps.list_ws, h->ps.list_b0, h->ps.ws,    h->ps.ws_need,  st.rtab,        st.n0,
-                  h->d_defer, h->d_hc,       h->d_hc_count,  h->d_hc_fail,   h->d_roll_prog};
+                  h->d_defer, h->d_hc,       h->d_hc_count,  h->d_hc_fail,   h->d_roll_prog,
+                  h->kg.ids[0], h->kg.ids[1], h->kg.vals[0], h->kg.vals[1],  h->kg.hist,     h->kg.sums,
+                  h->kg.call, h->kg_vals,    h->kg_offs};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (int c = 0; c < GK_MAX_CLASSES; ++c)
@@ -1436,7 +1468,7 @@ int gk_destroy(gk_set* h) {
   for (double* p : h->hc_buf) (void)hipHostFree(p);
   if (h->aux) (void)hipStreamDestroy(h->aux);
   for (void* p : {(void*)h->h_ws_need, (void*)h->h_ovf, (void*)h->h_ctr, (void*)h->h_qs, (void*)h->h_hc,
-                  (void*)h->h_hc_count, (void*)h->h_hc_flag})
+                  (void*)h->h_hc_count, (void*)h->h_hc_flag, (void*)h->h_kg})
     if (p) (void)hipHostFree(p);
   delete h;
   return GK_OK;
@@ -1488,6 +1520,125 @@ int gk_ingest(gk_set* h, const double* values, const int64_t* offsets, void* str
   const int rj = stats_join(h, s, GKQuery());  // joined on every path
   const int rd = mark_done(h, s, true);
   return rc ? rc : (rj ? rj : rd);
+}
+
+// The grouping scratch for `count` samples (and, grouped: the set-owned
+// grouped batch).  Growing synchronises `s` first: earlier launches may still
+// use the buffers (the caller has settled the last call: nothing is re-run
+// from them any more).
+static int ensure_group_scratch(gk_set* h, int64_t count, bool grouped, hipStream_t s) {
+  const int64_t n = std::max<int64_t>(count, 1);
+  // pass p writes ids[p & 1] and, unless it is the last, vals[p & 1]
+  const int passes = gk_group_passes(h->S), pairs = std::min(passes, 2), vbufs = std::min(passes - 1, 2);
+  const int64_t tiles = std::max<int64_t>(gk_group_tiles(n), 1), sums = gk_group_sums(n);
+  const bool first = !h->kg.call;
+  const bool grow_pairs = pairs > 0 && (n > h->kg_cap || pairs > h->kg_pairs), grow_hist = tiles > h->kg_tiles,
+             grow_sums = sums > h->kg_sums, grow_vals = grouped && (n > h->kg_vals_cap || !h->kg_offs);
+  if (!(first || grow_pairs || grow_hist || grow_sums || grow_vals)) return GK_OK;
+  HIP_TRY(hipStreamSynchronize(s));
+  auto renew = [](auto** p, size_t bytes) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    if (hipMalloc((void**)p, bytes) == hipSuccess) return true;
+    *p = nullptr;
+    (void)hipGetLastError();
+    return false;
+  };
+  bool ok = true;
+  if (first) {
+    // per-call words and, behind them, the cumulative block: one allocation
+    ok = renew(&h->kg.call, (GK_KG_CALL_WORDS + GK_KG_CUM_WORDS) * sizeof(unsigned long long)) &&
+         hipMemset(h->kg.call, 0, (GK_KG_CALL_WORDS + GK_KG_CUM_WORDS) * sizeof(unsigned long long)) == hipSuccess &&
+         hipHostMalloc(&h->h_kg, GK_KG_CUM_WORDS * sizeof(unsigned long long)) == hipSuccess;
+    if (ok) {
+      memset(h->h_kg, 0, GK_KG_CUM_WORDS * sizeof(unsigned long long));
+      h->kg.cum = h->kg.call + GK_KG_CALL_WORDS;
+    } else {
+      if (h->kg.call) (void)hipFree(h->kg.call);
+      h->kg.call = nullptr;
+    }
+  }
+  if (ok && grow_pairs) {
+    const int64_t cap = std::max(n, h->kg_cap);
+    h->kg_cap = 0;
+    h->kg_pairs = 0;
+    for (int k = 0; k < 2 && ok; ++k) {
+      if (k < pairs) ok = renew(&h->kg.ids[k], (size_t)cap * sizeof(int32_t));
+      if (ok && k < vbufs) ok = renew(&h->kg.vals[k], (size_t)cap * sizeof(double));
+    }
+    if (ok) {
+      h->kg_cap = cap;
+      h->kg_pairs = pairs;
+    }
+  }
+  if (ok && grow_hist) {
+    h->kg_tiles = 0;
+    ok = renew(&h->kg.hist, ((size_t)tiles << GK_GROUP_BITS) * sizeof(uint32_t));
+    if (ok) h->kg_tiles = tiles;
+  }
+  if (ok && grow_sums) {
+    h->kg_sums = 0;
+    ok = renew(&h->kg.sums, (size_t)sums * sizeof(unsigned long long));
+    if (ok) h->kg_sums = sums;
+  }
+  if (ok && grow_vals) {
+    const int64_t cap = std::max(n, h->kg_vals_cap);
+    h->kg_vals_cap = 0;
+    ok = renew(&h->kg_vals, (size_t)cap * sizeof(double)) &&
+         (h->kg_offs || renew(&h->kg_offs, (size_t)(h->S + 1) * sizeof(int64_t)));
+    if (ok) h->kg_vals_cap = cap;
+  }
+  if (!ok) return fail(GK_E_NOMEM, "grouping scratch for %lld samples failed", (long long)count);
+  return GK_OK;
+}
+
+static int check_keyed_args(const int32_t* ids, const double* values, int64_t count) {
+  if (count < 0 || count > INT32_MAX) return fail(GK_E_ARG, "count %lld outside [0, 2^31-1]", (long long)count);
+  if (count > 0 && (!ids || !values)) return fail(GK_E_ARG, "ids or values is null");
+  return GK_OK;
+}
+
+int gk_group_by_key(gk_set* h, const int32_t* ids, const double* values, int64_t count, double* out_values,
+                    int64_t* out_offsets, void* stream) {
+  int rc = check_set(h);
+  if (!rc) rc = check_keyed_args(ids, values, count);
+  if (rc) return rc;
+  if (!out_offsets) return fail(GK_E_ARG, "out_offsets is null");
+  if (count > 0 && !out_values) return fail(GK_E_ARG, "out_values is null");
+  hipStream_t s = (hipStream_t)stream;
+  rc = settle(h, s, false);
+  if (!rc) rc = take_sticky(h);
+  if (!rc) rc = ensure_group_scratch(h, count, false, s);
+  if (rc) return rc;
+  HIP_TRY(gk_launch_group_by_key(h->kg, ids, values, count, h->S, out_values, out_offsets, s));
+  return mark_done(h, s);  // (the bad-id block comes back with the counters)
+}
+
+int gk_ingest_keyed(gk_set* h, const int32_t* ids, const double* values, int64_t count, const double* qs, int nq,
+                    double* out, int mode, void* stream) {
+  int rc = check_set(h);
+  if (rc) return rc;
+  // (the checks of prepare_query, ahead of the grouping)
+  if (nq < 0 || (nq > 0 && (!qs || !out))) return fail(GK_E_ARG, "bad quantile arguments");
+  if (mode != GK_Q_LIST && mode != GK_Q_SINGLE) return fail(GK_E_ARG, "bad mode %d", mode);
+  for (int i = 0; i < nq; ++i)
+    if (std::isnan(qs[i])) return fail(GK_E_ARG, "cannot convert float NaN to integer");
+  rc = check_keyed_args(ids, values, count);
+  if (rc) return rc;
+  if (h->S == 0) return GK_OK;
+  hipStream_t s = (hipStream_t)stream;
+  // The last call is settled BEFORE the grouping is enqueued: its deferred
+  // streams are re-run from its inputs, which for a keyed call are kg_vals /
+  // kg_offs -- the buffers this grouping rewrites.
+  rc = grow_pools(h, s);
+  if (!rc) rc = take_sticky(h);
+  if (!rc) rc = ensure_group_scratch(h, count, true, s);
+  if (rc) return rc;
+  HIP_TRY(gk_launch_group_by_key(h->kg, ids, values, count, h->S, h->kg_vals, h->kg_offs, s));
+  // exactly the CSR path on the grouped batch (its own settle finds the last
+  // call settled; a bad id left kg_offs all zero: an empty batch)
+  if (nq == 0) return gk_ingest(h, h->kg_vals, h->kg_offs, stream);
+  return gk_ingest_quantiles(h, h->kg_vals, h->kg_offs, qs, nq, out, mode, stream);
 }
 
 int gk_flush(gk_set* h, void* stream) {

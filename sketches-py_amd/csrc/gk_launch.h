@@ -190,6 +190,36 @@ hipError_t gk_launch_rollup_check_members(const int64_t* members, int64_t M, int
 // the members with n != 0 (those the reference flushes) into list, *count of them (zeroed by the caller)
 hipError_t gk_launch_rollup_flush_list(const GKState& src, const int64_t* members, int64_t M, int32_t* count,
                                        int32_t* list, hipStream_t stream);
+// ---- keyed ingest (gk_keyed.hip): stable group-by of (id, value) samples ----
+// An LSD radix partition by stream id, GK_GROUP_BITS per pass over tiles of
+// GK_GROUP_TILE samples (one workgroup each).  The set owns the scratch:
+struct GKGroupScratch {
+  int32_t* ids[2] = {};   // ping-pong pair buffers, `count` entries each: pass p writes ids[p & 1]
+  double* vals[2] = {};   //   and (not the last pass, which writes the caller's values) vals[p & 1]
+  uint32_t* hist = nullptr;            // [2^GK_GROUP_BITS][tiles] digit counts, scanned in place
+  unsigned long long* sums = nullptr;  // tile sums of the scan (gk_group_sums entries)
+  unsigned long long* call = nullptr;  // GK_KG_CALL_WORDS words of this call (zeroed by the launcher)
+  unsigned long long* cum = nullptr;   // cumulative: [0] calls voided by an id >= S, [1] the last one's
+                                       //   first bad sample index, [2] its id
+};
+#define GK_GROUP_BITS 8
+#define GK_GROUP_TILE 4096
+#define GK_GROUP_SCAN_TILE 2048
+#define GK_KG_BAD 0     // ids >= S in this call
+#define GK_KG_BADKEY 1  // max of (count - index) over them
+#define GK_KG_KEPT 2    // samples with an id in [0, S)
+#define GK_KG_CALL_WORDS 4
+#define GK_KG_CUM_WORDS 3
+int gk_group_passes(int64_t S);  // ceil(bits(S - 1) / GK_GROUP_BITS), at least 1
+inline int64_t gk_group_tiles(int64_t count) { return (count + GK_GROUP_TILE - 1) / GK_GROUP_TILE; }
+inline int64_t gk_group_sums(int64_t count) {
+  return ((gk_group_tiles(count) << GK_GROUP_BITS) + GK_GROUP_SCAN_TILE - 1) / GK_GROUP_SCAN_TILE;
+}
+// out_offsets (int64[S + 1]) and out_values (count doubles) from ids / values
+// (count samples, 0 <= count < 2^31); every kernel of a call that met an
+// id >= S leaves its outputs alone, except that out_offsets becomes all zero.
+hipError_t gk_launch_group_by_key(const GKGroupScratch& sc, const int32_t* ids, const double* values, int64_t count,
+                                  int64_t S, double* out_values, int64_t* out_offsets, hipStream_t stream);
 // every stream back to an empty sketch in class 0; ctr: also zero the set's
 // counter words [0, GK_CTR_FATAL) (slots used, member-list lengths) and the
 // per-call block [GK_CTR_CALL, GK_CALL_BYTES) (what begin_call's memset zeroes)

@@ -53,6 +53,8 @@ SYMBOLS = {
     "gk_destroy": (_INT, [_P]),
     "gk_reset": (_INT, [_P, _P]),
     "gk_ingest": (_INT, [_P, _P, _P, _P]),
+    "gk_group_by_key": (_INT, [_P, _P, _P, _I64, _P, _P, _P]),
+    "gk_ingest_keyed": (_INT, [_P, _P, _P, _I64, ctypes.POINTER(_D), _INT, _P, _INT, _P]),
     "gk_flush": (_INT, [_P, _P]),
     "gk_sync": (_INT, [_P, _P]),
     "gk_quantiles": (_INT, [_P, ctypes.POINTER(_D), _INT, _P, _INT, _P]),

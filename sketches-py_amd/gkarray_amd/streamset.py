@@ -189,6 +189,79 @@ class StreamSet:
             self.sync()
         return out[:, :nq]
 
+    # ------------------------------------------------------------ keyed ingest
+    def _keyed_args(self, ids, values):
+        """(ids int32, values float64) on the set's device, checked."""
+        i = torch.as_tensor(ids)
+        v = torch.as_tensor(values)
+        if i.dim() != 1 or v.dim() != 1:
+            raise ValueError("ids and values must be one-dimensional")
+        if i.numel() != v.numel():
+            raise ValueError("ids and values must have the same length (%d vs %d)" % (i.numel(), v.numel()))
+        if i.numel() > 2 ** 31 - 1:
+            raise ValueError("at most 2^31-1 samples per call")
+        if i.dtype == torch.int32:
+            pass
+        elif i.dtype == torch.int64 or (i.numel() == 0 and not i.dtype.is_floating_point):
+            # the C ABI takes int32 ids: one range check (an id beyond int32
+            # would wrap into a valid stream) and one conversion pass
+            if i.numel() and (int(i.max().item()) > 2 ** 31 - 1 or int(i.min().item()) < -2 ** 31):
+                raise ValueError("an id does not fit int32")
+            i = i.to(torch.int32)
+        else:
+            raise ValueError("ids must be int32 or int64, got %s" % i.dtype)
+        return self._dev(i, torch.int32), self._dev(v, torch.float64)
+
+    def group_by_key(self, ids, values):
+        """Stable group-by of samples in arrival order (``gk_group_by_key``):
+        returns ``(values_grouped, offsets)`` such that stream s owns
+        ``values_grouped[offsets[s]:offsets[s+1]]``, the values whose id is s
+        in ascending sample index, copied bit for bit -- the CSR batch
+        ``ingest`` takes.  Negative ids are skipped; an id >= num_streams
+        raises ``GKBackendError`` (GK_E_ARG).  ``ids`` is int32, or int64 at
+        the cost of a range check and a conversion pass."""
+        i, v = self._keyed_args(ids, values)
+        n = i.numel()
+        out = torch.empty(max(n, 1), dtype=torch.float64, device=self.device)
+        offs = torch.empty(self.num_streams + 1, dtype=torch.int64, device=self.device)
+        with self._ctx():
+            self._check(self._lib.gk_group_by_key(self._h, _ptr(i) if n else None, _ptr(v) if n else None, n,
+                                                  _ptr(out), _ptr(offs), self._sp()))
+        self._inflight = (i, v, out, offs)
+        self.sync()
+        return out[:int(offs[-1].item())], offs
+
+    def ingest_keyed(self, ids, values, quantiles=None, single=False, sync=True):
+        """``for i in range(len(ids)): self[ids[i]].add(values[i])`` (gk:49-61)
+        in one call on unsorted device arrays (``gk_ingest_keyed``): the
+        samples are grouped by a stable sort on the device and go through the
+        path of ``ingest``.  Negative ids are skipped.  An id >= num_streams
+        voids the call (no value is added; a fused query answers from the
+        state before the call) and raises ``GKBackendError`` (GK_E_ARG), at
+        ``sync()`` at the latest.  ``quantiles``, ``single`` and ``sync`` as
+        ``ingest``; ``ids`` as ``group_by_key``."""
+        i, v = self._keyed_args(ids, values)
+        n = i.numel()
+        pi, pv = (_ptr(i), _ptr(v)) if n else (None, None)
+        if quantiles is None:
+            with self._ctx():
+                self._check(self._lib.gk_ingest_keyed(self._h, pi, pv, n, None, 0, None, L.GK_Q_LIST, self._sp()))
+            self._inflight = (i, v)
+            if sync:
+                self.sync()
+            return None
+        qs = [float(q) for q in quantiles]
+        nq = len(qs)
+        out = torch.empty((self.num_streams, max(nq, 1)), dtype=torch.float64, device=self.device)
+        arr = (ctypes.c_double * max(nq, 1))(*qs)
+        mode = L.GK_Q_SINGLE if single else L.GK_Q_LIST
+        with self._ctx():
+            self._check(self._lib.gk_ingest_keyed(self._h, pi, pv, n, arr, nq, _ptr(out), mode, self._sp()))
+        self._inflight = (i, v, out)
+        if sync:
+            self.sync()
+        return out[:, :nq]
+
     def ingest_lists(self, seqs):
         """Convenience: ``seqs[s]`` is the list of values for stream s."""
         if len(seqs) != self.num_streams:
