@@ -34,7 +34,8 @@
  *    buffers alive and unchanged until the set's next call or gk_sync: a
  *    stream that needs a class whose arena has no free slot yet is deferred
  *    and re-run from them by the host runtime before the next call proceeds.
- *    gk_merge, gk_rollup,
+ *    gk_merge, gk_rollup, gk_quantiles_select, gk_flush_select,
+ *    gk_reset_select, gk_stats_select,
  *    gk_merge_compress, gk_import, gk_save / gk_load and gk_num_promoted
  *    synchronise before returning.
  *  - Limits.  Any finite eps > 0 with int(1/eps)+1 < 2^24 is accepted (the
@@ -176,6 +177,65 @@ int gk_ingest_quantiles(gk_set* set, const double* values, const int64_t* offset
  * Any pointer may be NULL.  All outputs are device arrays of length S. */
 int gk_stats(gk_set* set, int64_t* n, double* mn, double* mx, double* sum,
              double* avg, int32_t* table_size, int32_t* pending, void* stream);
+
+/* Per-stream selection: query, flush, reset and stats of a LIST of streams,
+ * what the reference's user does on a dict of GKArray objects one key at a
+ * time (sketches[k].quantiles(qs); sketches[k] = GKArray(eps); sketches[k]._n).
+ * gk_quantiles / gk_flush / gk_reset / gk_stats work on every stream of the
+ * set; these touch only the streams listed in ids[0 .. count).
+ *  - Memory.  `ids` (int32), `out` and the stats outputs are device memory
+ *    for the GPU engine, host memory for the CPU engine.  `qs` is host memory,
+ *    as in gk_quantiles.
+ *  - Count.  0 <= count <= 2^31-1, anything else is GK_E_ARG.  count == 0
+ *    returns GK_OK and touches no stream (`ids` may then be NULL); a NULL `ids`
+ *    with count > 0 is GK_E_ARG.
+ *  - Bad ids.  An id outside [0, S) -- negative ids included: a query has no
+ *    "not for this set" row -- is GK_E_ARG, returned by the call itself BEFORE
+ *    anything is mutated or written, with the first bad index and its id in
+ *    the message.
+ *  - Duplicates.  Ids may repeat and come in any order.  Row k of an output
+ *    always belongs to ids[k]; a stream listed twice is flushed or reset once
+ *    and answered twice with the same bits.
+ *  - Synchronisation.  All four calls synchronise before returning, after
+ *    settling the set's earlier asynchronous work and errors (gk_sync first,
+ *    as gk_rollup does: deferred streams of the previous call are re-run, a
+ *    sticky error of it is returned instead of doing the work).
+ *  - Unlisted streams stay bit-identical: table, pending values and
+ *    n/_min/_max/_sum/_avg (GPU engine: also capacity class and slot).
+ *
+ * gk_quantiles_select: `out` is float64[count*nq], row-major [k][q]; row k is
+ *   GKArray.quantiles(qs) (GK_Q_LIST) or quantile(q) for every q (GK_Q_SINGLE)
+ *   of stream ids[k], with the argument checks and the effective mode of
+ *   gk_quantiles (NaN in qs: GK_E_ARG; an unsorted list is answered per q).
+ *   nq == 0 returns GK_OK after the id check and touches nothing.  Flush rule:
+ *   gk_quantiles' rule restricted to the listed streams -- a listed stream
+ *   with n > 0 and pending values runs merge_compress() first (gk:166-167,
+ *   gk:197-198); a listed stream without pending values is NOT compressed
+ *   again (gk_rollup, by contrast, flushes its members unconditionally).  A
+ *   listed stream whose flush outgrows its capacity class moves up, as
+ *   roll-up members do; one that outgrows the last class makes the call
+ *   return GK_E_OVERFLOW: that stream keeps its pre-call state, the other
+ *   listed streams have been flushed, `out` is not written.
+ * gk_flush_select: that flush and nothing else -- what size() does first
+ *   (gk:45-46).
+ * gk_reset_select: each listed stream goes back to GKArray(eps) (gk:21-29):
+ *   empty table, no pending values, n = 0, min = +inf, max = -inf, sum = avg
+ *   = 0.  On the GPU engine a reset stream KEEPS its capacity class and slot
+ *   (arenas are bump-allocated and the class member lists have no removal):
+ *   memory is not returned and gk_num_promoted does not drop.  gk_reset is the
+ *   call that gives everything back.
+ * gk_stats_select: gk_stats' seven arrays gathered at ids into outputs of
+ *   length `count`; any output pointer may be NULL.  Does not flush.
+ *  - Scratch (GPU engine; owned by the set, only grows, freed by gk_destroy):
+ *    S/8 bytes + 4 bytes per listed id (at most 4 S).  GK_E_NOMEM is returned
+ *    before anything is mutated. */
+int gk_quantiles_select(gk_set* set, const int32_t* ids, int64_t count,
+                        const double* qs, int nq, double* out, int mode, void* stream);
+int gk_flush_select(gk_set* set, const int32_t* ids, int64_t count, void* stream);
+int gk_reset_select(gk_set* set, const int32_t* ids, int64_t count, void* stream);
+int gk_stats_select(gk_set* set, const int32_t* ids, int64_t count,
+                    int64_t* n, double* mn, double* mx, double* sum, double* avg,
+                    int32_t* table_size, int32_t* pending, void* stream);
 
 /* GKArray.merge(other) (gk:111-154), stream by stream, as the left fold
  * dst.merge(srcs[0]); dst.merge(srcs[1]); ...  Like the reference it mutates

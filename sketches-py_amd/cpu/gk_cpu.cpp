@@ -614,6 +614,102 @@ int gk_stats(gk_set* h, int64_t* n, double* mn, double* mx, double* sum, double*
   return GK_OK;
 }
 
+// ---- per-stream selection: query, flush, reset and stats of a list of streams
+
+// count and ids checked (every id in [0, S)) before anything is mutated
+static int check_select(const gk_set* h, const int32_t* ids, int64_t count) {
+  if (count < 0 || count > INT32_MAX) return fail(GK_E_ARG, "count %lld outside [0, 2^31-1]", (long long)count);
+  if (count > 0 && !ids) return fail(GK_E_ARG, "ids is null");
+  for (int64_t k = 0; k < count; ++k)
+    if (ids[k] < 0 || ids[k] >= h->S)
+      return fail(GK_E_ARG, "ids[%lld] = %d lies outside [0, %lld)", (long long)k, ids[k], (long long)h->S);
+  return GK_OK;
+}
+
+// the DISTINCT listed streams (two threads never work on one Stream)
+static int distinct_ids(const gk_set* h, const int32_t* ids, int64_t count, std::vector<int32_t>& out) {
+  try {
+    std::vector<bool> seen((size_t)h->S, false);
+    out.clear();
+    for (int64_t k = 0; k < count; ++k) {
+      if (seen[(size_t)ids[k]]) continue;
+      seen[(size_t)ids[k]] = true;
+      out.push_back(ids[k]);
+    }
+  } catch (...) {
+    return fail(GK_E_NOMEM, "selection scratch for %lld streams failed", (long long)h->S);
+  }
+  return GK_OK;
+}
+
+// merge_compress() of the listed streams with n > 0 and pending values
+// (gk:45-46, 166-167, 197-198), each once
+static int flush_selected(gk_set* h, const int32_t* ids, int64_t count) {
+  std::vector<int32_t> uniq;
+  int rc = distinct_ids(h, ids, count, uniq);
+  if (rc) return rc;
+  parallel_for((int64_t)uniq.size(), h->threads, [&](int64_t k) {
+    Stream& st = h->st[uniq[k]];
+    if (st.n > 0) flush_if_pending(h, st);
+  });
+  return GK_OK;
+}
+
+int gk_flush_select(gk_set* h, const int32_t* ids, int64_t count, void* stream) {
+  (void)stream;
+  int rc = check_set(h);
+  if (!rc) rc = check_select(h, ids, count);
+  if (rc || count == 0) return rc;
+  return flush_selected(h, ids, count);
+}
+
+int gk_quantiles_select(gk_set* h, const int32_t* ids, int64_t count, const double* qs, int nq, double* out, int mode,
+                        void* stream) {
+  (void)stream;
+  int rc = check_set(h);
+  if (!rc) rc = check_query(qs, nq, out, mode);
+  if (!rc) rc = check_select(h, ids, count);
+  if (rc || count == 0 || nq == 0) return rc;
+  mode = effective_mode(qs, nq, mode);
+  rc = flush_selected(h, ids, count);
+  if (rc) return rc;
+  // (read-only from here: rows of a repeated stream may be answered in parallel)
+  parallel_for(count, h->threads,
+               [&](int64_t k) { answer(h, h->st[ids[k]], qs, nq, mode, out + k * (int64_t)nq); });
+  return GK_OK;
+}
+
+int gk_reset_select(gk_set* h, const int32_t* ids, int64_t count, void* stream) {
+  (void)stream;
+  int rc = check_set(h);
+  if (!rc) rc = check_select(h, ids, count);
+  if (rc || count == 0) return rc;
+  std::vector<int32_t> uniq;
+  rc = distinct_ids(h, ids, count, uniq);
+  if (rc) return rc;
+  parallel_for((int64_t)uniq.size(), h->threads, [&](int64_t k) { h->st[uniq[k]] = Stream(); });
+  return GK_OK;
+}
+
+int gk_stats_select(gk_set* h, const int32_t* ids, int64_t count, int64_t* n, double* mn, double* mx, double* sum,
+                    double* avg, int32_t* table_size, int32_t* pending, void* stream) {
+  (void)stream;
+  int rc = check_set(h);
+  if (!rc) rc = check_select(h, ids, count);
+  if (rc) return rc;
+  for (int64_t k = 0; k < count; ++k) {
+    const Stream& st = h->st[ids[k]];
+    if (n) n[k] = st.n;
+    if (mn) mn[k] = st.mn;
+    if (mx) mx[k] = st.mx;
+    if (sum) sum[k] = st.sum;
+    if (avg) avg[k] = st.avg;
+    if (table_size) table_size[k] = (int32_t)st.tab.size();
+    if (pending) pending[k] = (int32_t)st.pend.size();
+  }
+  return GK_OK;
+}
+
 int gk_merge(gk_set* dst, gk_set* const* srcs, int nsrcs, void* stream) {
   (void)stream;
   int rc = check_set(dst);

@@ -164,6 +164,11 @@ struct gk_set {
   int64_t* kg_offs = nullptr;
   unsigned long long* h_kg = nullptr;  // pinned GK_KG_CUM_WORDS words
   unsigned long long kg_bad_seen = 0;  // voided keyed calls already reported
+  // Per-stream selection (gk_*_select; made on first use, only grown, freed in
+  // gk_destroy): GK_SEL_WORDS control words, the bitmap of listed streams and
+  // the flush list (k_select_check)
+  int32_t* d_sel = nullptr;
+  int64_t sel_words = 0;
   // Host-walked chains: the gk:52-59 chains of the
   // longest streams run on host cores beside the GPU ingest.  hc_min: shortest
   // stream taken (0: off; GK_HOST_CHAINS=0 / GK_HOST_CHAIN_MIN); hc_threads:
@@ -1446,7 +1451,7 @@ int gk_destroy(gk_set* h) {
                   h->ps.list_ws, h->ps.list_b0, h->ps.ws,    h->ps.ws_need,  st.rtab,        st.n0,
                   h->d_defer, h->d_hc,       h->d_hc_count,  h->d_hc_fail,   h->d_roll_prog,
                   h->kg.ids[0], h->kg.ids[1], h->kg.vals[0], h->kg.vals[1],  h->kg.hist,     h->kg.sums,
-                  h->kg.call, h->kg_vals,    h->kg_offs};
+                  h->kg.call, h->kg_vals,    h->kg_offs,     h->d_sel};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (int c = 0; c < GK_MAX_CLASSES; ++c)
@@ -1777,6 +1782,162 @@ int gk_stats(gk_set* h, int64_t* n, double* mn, double* mx, double* sum, double*
   if (avg) HIP_TRY(hipMemcpyAsync(avg, h->st.avg, S * sizeof(double), hipMemcpyDeviceToDevice, s));
   if (table_size) HIP_TRY(hipMemcpyAsync(table_size, h->st.E, S * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   if (pending) HIP_TRY(hipMemcpyAsync(pending, h->st.pend, S * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  return GK_OK;
+}
+
+// ---- per-stream selection: query, flush, reset and stats of a list of streams
+
+static int check_select_args(const int32_t* ids, int64_t count) {
+  if (count < 0 || count > INT32_MAX) return fail(GK_E_ARG, "count %lld outside [0, 2^31-1]", (long long)count);
+  if (count > 0 && !ids) return fail(GK_E_ARG, "ids is null");
+  return GK_OK;
+}
+
+static int64_t select_bitmap_words(const gk_set* h, bool want_list) { return want_list ? (h->S + 31) / 32 : 0; }
+
+// The selection scratch: k_select_check's control words, then (want_list) the
+// bitmap of listed streams and the flush list, both live at once.  Only grows;
+// the caller has synchronised `s` (nothing enqueued uses the old buffer).
+static int ensure_select_scratch(gk_set* h, int64_t count, bool want_list) {
+  const int64_t words =
+      GK_SEL_WORDS + select_bitmap_words(h, want_list) + (want_list ? std::min<int64_t>(count, h->S) : 0);
+  if (words <= h->sel_words) return GK_OK;
+  if (h->d_sel) (void)hipFree(h->d_sel);
+  h->d_sel = nullptr;
+  h->sel_words = 0;
+  if (hipMalloc(&h->d_sel, (size_t)words * sizeof(int32_t)) != hipSuccess) {
+    h->d_sel = nullptr;
+    (void)hipGetLastError();
+    return fail(GK_E_NOMEM, "selection scratch of %lld words failed", (long long)words);
+  }
+  h->sel_words = words;
+  return GK_OK;
+}
+
+// Head of every selection call, count > 0: the set's earlier work is settled
+// (gk_sync: deferred streams re-run, sticky errors returned), then ONE kernel
+// over ids checks their range and (want_list) lists the streams to flush --
+// nothing is mutated before its verdict has been read back.
+static int select_begin(gk_set* h, const int32_t* ids, int64_t count, bool want_list, void* stream, int32_t** list,
+                        int64_t* nflush) {
+  hipStream_t s = (hipStream_t)stream;
+  int rc = ensure_select_scratch(h, count, want_list);
+  if (rc) return rc;
+  const int64_t bm = select_bitmap_words(h, want_list);
+  int32_t* const ctl = h->d_sel;
+  uint32_t* const bitmap = reinterpret_cast<uint32_t*>(ctl + GK_SEL_WORDS);
+  *list = want_list ? ctl + GK_SEL_WORDS + bm : nullptr;
+  HIP_TRY(hipMemsetAsync(ctl, 0, (size_t)(GK_SEL_WORDS + bm) * sizeof(int32_t), s));
+  HIP_TRY(gk_launch_select_check(h->st, ids, count, ctl, bitmap, *list, s));
+  HIP_TRY(hipMemcpyAsync(h->h_ovf, ctl, GK_SEL_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (h->h_ovf[GK_SEL_BAD]) {
+    const int64_t first = count - (int64_t)(uint32_t)h->h_ovf[GK_SEL_FIRST];
+    int32_t id = 0;
+    HIP_TRY(hipMemcpy(&id, ids + first, sizeof(int32_t), hipMemcpyDeviceToHost));
+    return fail(GK_E_ARG, "ids[%lld] = %d lies outside [0, %lld)", (long long)first, id, (long long)h->S);
+  }
+  *nflush = h->h_ovf[GK_SEL_COUNT];
+  return GK_OK;
+}
+
+// merge_compress() of the listed streams (each has n > 0 and pending values):
+// k_merge's explicit-record mode with no records, as gk_rollup flushes its
+// members; a stream that needs a larger class for it climbs run_merge's levels.
+static int select_flush(gk_set* h, const int32_t* list, int64_t nflush, hipStream_t s) {
+  if (nflush <= 0) return GK_OK;
+  MergeArgsHost a{};
+  a.src = h->st;
+  a.eoffs = h->d_zero_offs;
+  a.mode = 1;
+  a.list = list;
+  a.count = nflush;
+  return run_merge(h, a, s);
+}
+
+// End of a selection call that may have promoted streams: the counters (slots
+// in use) come back for the next call's grow_pools, and the call synchronises.
+static int select_end(gk_set* h, hipStream_t s) {
+  int rc = mark_done(h, s);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(s));
+  poll(h, true);
+  return GK_OK;
+}
+
+int gk_flush_select(gk_set* h, const int32_t* ids, int64_t count, void* stream) {
+  int rc = check_set(h);
+  if (!rc) rc = check_select_args(ids, count);
+  if (!rc) rc = gk_sync(h, stream);
+  if (rc || count == 0) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* list = nullptr;
+  int64_t nflush = 0;
+  rc = select_begin(h, ids, count, true, stream, &list, &nflush);
+  if (rc || nflush == 0) return rc;
+  rc = select_flush(h, list, nflush, s);
+  return rc ? rc : select_end(h, s);
+}
+
+int gk_quantiles_select(gk_set* h, const int32_t* ids, int64_t count, const double* qs, int nq, double* out, int mode,
+                        void* stream) {
+  int rc = check_set(h);
+  if (!rc) rc = check_select_args(ids, count);
+  if (rc) return rc;
+  // (the checks of prepare_query, ahead of anything else)
+  if (nq < 0 || (nq > 0 && (!qs || !out))) return fail(GK_E_ARG, "bad quantile arguments");
+  if (mode != GK_Q_LIST && mode != GK_Q_SINGLE) return fail(GK_E_ARG, "bad mode %d", mode);
+  for (int i = 0; i < nq; ++i)
+    if (std::isnan(qs[i])) return fail(GK_E_ARG, "cannot convert float NaN to integer");
+  rc = gk_sync(h, stream);
+  if (rc || count == 0) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* list = nullptr;
+  int64_t nflush = 0;
+  rc = select_begin(h, ids, count, true, stream, &list, &nflush);
+  if (rc || nq == 0) return rc;
+  GKQuery q;
+  rc = prepare_query(h, qs, nq, out, mode, s, &q);  // (before the flush: its GK_E_NOMEM mutates nothing)
+  if (rc) return rc;
+  // gk:166-167 / gk:197-198: the listed streams with pending values are
+  // flushed first (state mutation); then every row from its committed table
+  rc = select_flush(h, list, nflush, s);
+  if (rc) return rc;  // (GK_E_OVERFLOW: out is not written)
+  HIP_TRY(gk_launch_select_query(h->st, ids, count, q, s));
+  return select_end(h, s);
+}
+
+int gk_reset_select(gk_set* h, const int32_t* ids, int64_t count, void* stream) {
+  int rc = check_set(h);
+  if (!rc) rc = check_select_args(ids, count);
+  if (!rc) rc = gk_sync(h, stream);
+  if (rc || count == 0) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* list = nullptr;
+  int64_t nflush = 0;
+  rc = select_begin(h, ids, count, false, stream, &list, &nflush);
+  if (rc) return rc;
+  // (class and slot stay: the stream's next ingest runs in its class's launch,
+  // from an empty table)
+  HIP_TRY(gk_launch_select_reset(h->st, ids, count, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return GK_OK;
+}
+
+int gk_stats_select(gk_set* h, const int32_t* ids, int64_t count, int64_t* n, double* mn, double* mx, double* sum,
+                    double* avg, int32_t* table_size, int32_t* pending, void* stream) {
+  int rc = check_set(h);
+  if (!rc) rc = check_select_args(ids, count);
+  if (!rc) rc = gk_sync(h, stream);
+  if (rc || count == 0) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* list = nullptr;
+  int64_t nflush = 0;
+  rc = select_begin(h, ids, count, false, stream, &list, &nflush);
+  if (rc) return rc;
+  const GKSelectStats o{n, mn, mx, sum, avg, table_size, pending};
+  HIP_TRY(gk_launch_select_stats(h->st, ids, count, o, s));
+  HIP_TRY(hipStreamSynchronize(s));
   return GK_OK;
 }
 

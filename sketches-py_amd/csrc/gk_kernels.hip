@@ -15,6 +15,8 @@
 //                           as a count over the running max of prefix(g)+delta
 //   k_merge      gk:111-154 wave per stream: convert `other`, stable merge of
 //                           the incoming list, general four-rule walk (gk:76-106)
+//   k_select_*   gk:156-232, 45-46, 21-29  a list of stream ids: id check + flush
+//                           list, wave per row query, reset, stats gather
 //   k_export / k_import / k_reset: state movement
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -5314,6 +5316,89 @@ __global__ void k_rollup_flush_list(GKState src, const int64_t* __restrict__ mem
 }
 
 // ===========================================================================
+// Per-stream selection (gk_quantiles_select / gk_flush_select /
+// gk_reset_select / gk_stats_select): the calls take a list `ids` of `count`
+// stream ids, in any order, repeats allowed.
+// ===========================================================================
+// k_select_check: the id check and, list != NULL (flush / query), the flush
+// list, in one pass over ids that mutates no stream state -- one readback of
+// ctl gives the verdict and the list length before anything is changed.
+//  * an id outside [0, S): ctl[GK_SEL_BAD] is set and ctl[GK_SEL_FIRST] takes
+//    the maximum of count - k over the bad positions k (count minus the FIRST
+//    bad index: an atomicMax over words the caller zeroed);
+//  * a listed stream with n > 0 and pending values -- the streams that
+//    quantile() / quantiles() / size() flush first, gk:45-46, 166-167, 197-198
+//    -- joins `list` ONCE (bitmap: one bit per stream, zeroed by the caller),
+//    ctl[GK_SEL_COUNT] of them.  A stream without pending values is not
+//    listed: it is not compressed again.
+__global__ void k_select_check(GKState st, const int32_t* __restrict__ ids, int64_t count, int32_t* __restrict__ ctl,
+                               uint32_t* __restrict__ bitmap, int32_t* __restrict__ list) {
+  const int64_t step = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += step) {
+    const int64_t s = ids[k];
+    if (s < 0 || s >= st.S) {
+      atomicOr(&ctl[GK_SEL_BAD], 1);
+      atomicMax(reinterpret_cast<uint32_t*>(&ctl[GK_SEL_FIRST]), (uint32_t)(count - k));
+      continue;
+    }
+    if (!list || st.n[s] <= 0 || st.pend[s] <= 0) continue;
+    const uint32_t bit = 1u << (s & 31);
+    if (!(atomicOr(&bitmap[s >> 5], bit) & bit)) list[atomicAdd(&ctl[GK_SEL_COUNT], 1)] = (int32_t)s;
+  }
+}
+
+// k_select_query: row k of out = quantiles (gk:156-232) of stream ids[k] from
+// its committed table, one wave per row (a stream listed twice is answered
+// twice from the same table).  The call has synchronised after its flush:
+// _min/_max are final, so no marker pass as in k_query_list.
+__global__ __launch_bounds__(256) void k_select_query(GKState st, const int32_t* __restrict__ ids, int64_t count,
+                                                      const double* __restrict__ qs, int nq, int qmode,
+                                                      double* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wid = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwv = (int64_t)gridDim.x * 4;
+  for (int64_t k = wid; k < count; k += nwv) {
+    const int64_t s = ids[k];
+    const GKRec* tab = gk_table_ptr(st, s);
+    wave_quantiles<2, 4>(&tab->v, &tab->g, &tab->d, st.E[s], st.n[s], st.mn[s], st.mx[s], st, qs, nq, qmode,
+                         out + k * (int64_t)nq, lane);
+  }
+}
+
+// k_select_reset: every listed stream back to GKArray(eps) (gk:21-29), the
+// header values of k_reset -- but cls and slot stay: arenas are bump-allocated
+// and the class member lists have no removal, so a stream put back in class 0
+// would be listed twice after its next promotion.  (A repeated id writes the
+// same values twice.)
+__global__ void k_select_reset(GKState st, const int32_t* __restrict__ ids, int64_t count) {
+  const int64_t step = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += step) {
+    const int64_t s = ids[k];
+    st.n[s] = 0;
+    st.E[s] = 0;
+    st.pend[s] = 0;
+    st.mn[s] = __longlong_as_double(0x7ff0000000000000LL);   // +inf (gk:25)
+    st.mx[s] = __longlong_as_double((long long)0xfff0000000000000ULL);  // -inf (gk:26)
+    st.sum[s] = 0.0;
+    st.avg[s] = 0.0;
+  }
+}
+
+// k_select_stats: gk_stats' arrays gathered at ids (any output may be NULL)
+__global__ void k_select_stats(GKState st, const int32_t* __restrict__ ids, int64_t count, GKSelectStats o) {
+  const int64_t step = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += step) {
+    const int64_t s = ids[k];
+    if (o.n) o.n[k] = st.n[s];
+    if (o.mn) o.mn[k] = st.mn[s];
+    if (o.mx) o.mx[k] = st.mx[s];
+    if (o.sum) o.sum[k] = st.sum[s];
+    if (o.avg) o.avg[k] = st.avg[s];
+    if (o.table_size) o.table_size[k] = st.E[s];
+    if (o.pending) o.pending[k] = st.pend[s];
+  }
+}
+
+// ===========================================================================
 // state movement
 // ===========================================================================
 // ctr (gk_reset): the set's slot and member-list counters start over too
@@ -5951,6 +6036,37 @@ static int64_t wave_grid(int64_t S) {
   if (g > cap) g = cap;
   if (g < 1) g = 1;
   return g;
+}
+
+// one thread per listed id, at most 2^16 blocks (the kernels loop)
+static unsigned select_grid(int64_t count) { return (unsigned)std::min<int64_t>((count + 255) / 256, 65536); }
+
+hipError_t gk_launch_select_check(const GKState& st, const int32_t* ids, int64_t count, int32_t* ctl, uint32_t* bitmap,
+                                  int32_t* list, hipStream_t stream) {
+  if (count <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_select_check, dim3(select_grid(count)), dim3(256), 0, stream, st, ids, count, ctl, bitmap, list);
+  return hipGetLastError();
+}
+
+hipError_t gk_launch_select_query(const GKState& st, const int32_t* ids, int64_t count, const GKQuery& q,
+                                  hipStream_t stream) {
+  if (count <= 0 || !q.qs || q.nq <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_select_query, dim3((unsigned)wave_grid(count)), dim3(256), 0, stream, st, ids, count, q.qs,
+                     q.nq, q.mode, q.out);
+  return hipGetLastError();
+}
+
+hipError_t gk_launch_select_reset(const GKState& st, const int32_t* ids, int64_t count, hipStream_t stream) {
+  if (count <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_select_reset, dim3(select_grid(count)), dim3(256), 0, stream, st, ids, count);
+  return hipGetLastError();
+}
+
+hipError_t gk_launch_select_stats(const GKState& st, const int32_t* ids, int64_t count, const GKSelectStats& o,
+                                  hipStream_t stream) {
+  if (count <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_select_stats, dim3(select_grid(count)), dim3(256), 0, stream, st, ids, count, o);
+  return hipGetLastError();
 }
 
 hipError_t gk_launch_export(const GKState& st, const int64_t* offs, double* v, int32_t* g, int32_t* d,

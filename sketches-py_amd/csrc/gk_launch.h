@@ -190,6 +190,34 @@ hipError_t gk_launch_rollup_check_members(const int64_t* members, int64_t M, int
 // the members with n != 0 (those the reference flushes) into list, *count of them (zeroed by the caller)
 hipError_t gk_launch_rollup_flush_list(const GKState& src, const int64_t* members, int64_t M, int32_t* count,
                                        int32_t* list, hipStream_t stream);
+// ---- per-stream selection (gk_*_select): ids = `count` stream ids (device) ----
+// Control words of k_select_check (zeroed by the caller with the bitmap):
+#define GK_SEL_BAD 0    // an id outside [0, S)
+#define GK_SEL_FIRST 1  // max of (count - index) over them: count minus the first bad index
+#define GK_SEL_COUNT 2  // entries of the flush list
+#define GK_SEL_WORDS 4
+// the id check and, list != NULL, the listed streams with n > 0 and pending
+// values into list, each once (bitmap: (S + 31) / 32 zeroed words; list: room
+// for min(count, S) entries).  Mutates no stream state.
+hipError_t gk_launch_select_check(const GKState& st, const int32_t* ids, int64_t count, int32_t* ctl, uint32_t* bitmap,
+                                  int32_t* list, hipStream_t stream);
+// q.out[k * nq ..] = the quantiles of stream ids[k] from its committed table
+hipError_t gk_launch_select_query(const GKState& st, const int32_t* ids, int64_t count, const GKQuery& q,
+                                  hipStream_t stream);
+// the listed streams back to empty sketches; class and slot stay as they are
+hipError_t gk_launch_select_reset(const GKState& st, const int32_t* ids, int64_t count, hipStream_t stream);
+// gk_stats' arrays gathered at ids (device arrays of `count` entries, any may be NULL)
+struct GKSelectStats {
+  int64_t* n;
+  double* mn;
+  double* mx;
+  double* sum;
+  double* avg;
+  int32_t* table_size;
+  int32_t* pending;
+};
+hipError_t gk_launch_select_stats(const GKState& st, const int32_t* ids, int64_t count, const GKSelectStats& o,
+                                  hipStream_t stream);
 // ---- keyed ingest (gk_keyed.hip): stable group-by of (id, value) samples ----
 // An LSD radix partition by stream id, GK_GROUP_BITS per pass over tiles of
 // GK_GROUP_TILE samples (one workgroup each).  The set owns the scratch:

@@ -60,6 +60,10 @@ SYMBOLS = {
     "gk_quantiles": (_INT, [_P, ctypes.POINTER(_D), _INT, _P, _INT, _P]),
     "gk_ingest_quantiles": (_INT, [_P, _P, _P, ctypes.POINTER(_D), _INT, _P, _INT, _P]),
     "gk_stats": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gk_quantiles_select": (_INT, [_P, _P, _I64, ctypes.POINTER(_D), _INT, _P, _INT, _P]),
+    "gk_flush_select": (_INT, [_P, _P, _I64, _P]),
+    "gk_reset_select": (_INT, [_P, _P, _I64, _P]),
+    "gk_stats_select": (_INT, [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gk_merge": (_INT, [_P, ctypes.POINTER(_P), _INT, _P]),
     "gk_rollup": (_INT, [_P, _P, _P, _P, _P]),
     "gk_merge_compress": (_INT, [_P, _P, _P, _P, _P, _P]),

@@ -200,6 +200,10 @@ class StreamSet:
             raise ValueError("ids and values must have the same length (%d vs %d)" % (i.numel(), v.numel()))
         if i.numel() > 2 ** 31 - 1:
             raise ValueError("at most 2^31-1 samples per call")
+        return self._ids_i32(i), self._dev(v, torch.float64)
+
+    def _ids_i32(self, i):
+        """A one-dimensional id tensor as int32 on the set's device."""
         if i.dtype == torch.int32:
             pass
         elif i.dtype == torch.int64 or (i.numel() == 0 and not i.dtype.is_floating_point):
@@ -210,7 +214,7 @@ class StreamSet:
             i = i.to(torch.int32)
         else:
             raise ValueError("ids must be int32 or int64, got %s" % i.dtype)
-        return self._dev(i, torch.int32), self._dev(v, torch.float64)
+        return self._dev(i, torch.int32)
 
     def group_by_key(self, ids, values):
         """Stable group-by of samples in arrival order (``gk_group_by_key``):
@@ -318,6 +322,80 @@ class StreamSet:
         if self.num_streams == 0:
             d = {k: v[:0] for k, v in d.items()}
         return d
+
+    # ------------------------------------------------------- per-stream selection
+    def _select_ids(self, ids):
+        """ids as int32 on the set's device, checked as ``_keyed_args`` checks them."""
+        i = torch.as_tensor(ids)
+        if i.dim() != 1:
+            raise ValueError("ids must be one-dimensional")
+        if i.numel() > 2 ** 31 - 1:
+            raise ValueError("at most 2^31-1 ids per call")
+        return self._ids_i32(i)
+
+    def quantiles_select(self, ids, qs, single=False):
+        """``self[ids[k]].quantiles(qs)`` for every k (``gk_quantiles_select``;
+        ``single=True``: ``quantile(q)`` for every q): a float64 device tensor
+        [len(ids), len(qs)], row k for ``ids[k]``.  Only the listed streams
+        with pending values are flushed (gk:166-167, 197-198); every other
+        stream of the set stays bit-identical.  Ids may repeat and come in any
+        order; an id outside [0, num_streams) raises ``GKBackendError``
+        (GK_E_ARG) before anything is changed.  ``ids`` is int32, or int64 at
+        the cost of a range check and a conversion."""
+        i = self._select_ids(ids)
+        K = i.numel()
+        qs = [float(q) for q in qs]
+        nq = len(qs)
+        out = torch.empty((max(K, 1), max(nq, 1)), dtype=torch.float64, device=self.device)
+        arr = (ctypes.c_double * max(nq, 1))(*qs)
+        mode = L.GK_Q_SINGLE if single else L.GK_Q_LIST
+        with self._ctx():
+            self._check(self._lib.gk_quantiles_select(self._h, _ptr(i) if K else None, K, arr, nq, _ptr(out), mode,
+                                                      self._sp()))
+        self._inflight = None  # (the call synchronised)
+        return out[:K, :nq]
+
+    def flush_select(self, ids):
+        """``merge_compress()`` of the listed streams that hold pending values
+        (``gk_flush_select``; what ``size()`` does first, gk:45-46)."""
+        i = self._select_ids(ids)
+        K = i.numel()
+        with self._ctx():
+            self._check(self._lib.gk_flush_select(self._h, _ptr(i) if K else None, K, self._sp()))
+        self._inflight = None
+
+    def reset_select(self, ids):
+        """The listed streams back to ``GKArray(eps)`` (gk:21-29), the set's
+        ``sketches[k] = GKArray(eps)`` (``gk_reset_select``).  On the GPU a
+        reset stream keeps its capacity class: no memory is returned."""
+        i = self._select_ids(ids)
+        K = i.numel()
+        with self._ctx():
+            self._check(self._lib.gk_reset_select(self._h, _ptr(i) if K else None, K, self._sp()))
+        self._inflight = None
+
+    def stats_select(self, ids):
+        """``stats()`` of the listed streams (``gk_stats_select``): a dict with
+        the keys of ``stats()``, each a device tensor of length len(ids), entry
+        k for ``ids[k]``.  Does not flush."""
+        i = self._select_ids(ids)
+        K = i.numel()
+        n = max(K, 1)
+        d = dict(
+            n=torch.empty(n, dtype=torch.int64, device=self.device),
+            min=torch.empty(n, dtype=torch.float64, device=self.device),
+            max=torch.empty(n, dtype=torch.float64, device=self.device),
+            sum=torch.empty(n, dtype=torch.float64, device=self.device),
+            avg=torch.empty(n, dtype=torch.float64, device=self.device),
+            size=torch.empty(n, dtype=torch.int32, device=self.device),
+            pending=torch.empty(n, dtype=torch.int32, device=self.device),
+        )
+        with self._ctx():
+            self._check(self._lib.gk_stats_select(self._h, _ptr(i) if K else None, K, _ptr(d["n"]), _ptr(d["min"]),
+                                                  _ptr(d["max"]), _ptr(d["sum"]), _ptr(d["avg"]), _ptr(d["size"]),
+                                                  _ptr(d["pending"]), self._sp()))
+        self._inflight = None
+        return {k: v[:K] for k, v in d.items()}
 
     # ------------------------------------------------------------------ export
     def tables(self):
