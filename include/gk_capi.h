@@ -35,7 +35,7 @@
  *    stream that needs a class whose arena has no free slot yet is deferred
  *    and re-run from them by the host runtime before the next call proceeds.
  *    gk_merge, gk_rollup, gk_quantiles_select, gk_flush_select,
- *    gk_reset_select, gk_stats_select,
+ *    gk_reset_select, gk_stats_select, gk_ranks, gk_ranks_select,
  *    gk_merge_compress, gk_import, gk_save / gk_load and gk_num_promoted
  *    synchronise before returning.
  *  - Limits.  Any finite eps > 0 with int(1/eps)+1 < 2^24 is accepted (the
@@ -236,6 +236,53 @@ int gk_reset_select(gk_set* set, const int32_t* ids, int64_t count, void* stream
 int gk_stats_select(gk_set* set, const int32_t* ids, int64_t count,
                     int64_t* n, double* mn, double* mx, double* sum, double* avg,
                     int32_t* table_size, int32_t* pending, void* stream);
+
+/* Rank queries: bounds on each stream's count of values <= x, the inverse of
+ * gk_quantiles.  The reference has no rank(); the answer is defined on the
+ * reference's state (entries, _n, _min, _max) and is integer-exact.
+ *  - Contract.  A stream, after the flush below, has the table (v_k, g_k, d_k),
+ *    k = 0..E-1 (ascending in v), and n, _min, _max.  G(k) = g_0 + .. + g_{k-1},
+ *    G(0) = 0.  rank(x) is the int64 pair (lo, hi), rules applied in this order:
+ *        n == 0     ->  (0, 0)
+ *        x <  _min  ->  (0, 0)
+ *        x >= _max  ->  (n, n)
+ *        otherwise, with i = #{k : v_k <= x}:
+ *            lo = max(G(i), 1)
+ *            hi = min(i < E ? G(i+1) + d_i - 1 : n,  n - 1)
+ *    Comparisons are IEEE (-0.0 == 0.0; +-inf are ordinary thresholds).
+ *    Thresholds are answered independently: any order, repeats allowed.  A
+ *    stream that was fed NaN values is outside the contract (the reference's
+ *    own _min/_max then depend on the order of the values).
+ *  - Meaning.  For a stream built by adds alone, lo <= #{values <= x} <= hi
+ *    and hi - lo <= 2 eps n.  After gk_merge, gk_rollup or gk_fold_packed the
+ *    reference's conversion (gk:135-147) no longer keeps the invariants the
+ *    bracket rests on: lo <= hi still holds, the true count may lie outside.
+ *    The pair is the formula on the table in every case, never "repaired".
+ *  - Memory.  `xs` (nx float64 values, no NaN) is host memory, as `qs` is.
+ *    `lo` and `hi` are int64[rows*nx], row-major [row][x], device memory for
+ *    the GPU engine, host memory for the CPU engine; rows are the S streams
+ *    (gk_ranks) or ids[k], k in [0, count) (gk_ranks_select).  One of `lo` and
+ *    `hi` may be NULL.
+ *  - GK_E_ARG, before anything is mutated or written: nx < 0; nx > 0 with
+ *    `xs` NULL or with both outputs NULL; a NaN in xs; count and ids as
+ *    gk_quantiles_select reports them (the first bad index and its id in the
+ *    message).  nx == 0 returns GK_OK after the argument and id checks and
+ *    touches no stream; so does count == 0.
+ *  - Flush rule: gk_quantiles' rule.  A covered stream (every stream; the
+ *    listed ones) with n > 0 and pending values runs merge_compress() first
+ *    (gk:166-167); one with nothing pending is NOT compressed again.  Ranks and
+ *    quantiles are then answered from the same table.  Unlisted streams stay
+ *    bit-identical, as for the other _select calls.
+ *  - GK_E_OVERFLOW: a covered stream whose flush outgrows the last capacity
+ *    class keeps its pre-call state, the other covered streams have been
+ *    flushed, `lo` and `hi` are not written.
+ *  - Synchronisation.  Both calls synchronise before returning, after settling
+ *    the set's earlier asynchronous work and errors (gk_sync first).  The
+ *    device copy of xs is made before the flush: its GK_E_NOMEM mutates
+ *    nothing. */
+int gk_ranks(gk_set* set, const double* xs, int nx, int64_t* lo, int64_t* hi, void* stream);
+int gk_ranks_select(gk_set* set, const int32_t* ids, int64_t count,
+                    const double* xs, int nx, int64_t* lo, int64_t* hi, void* stream);
 
 /* GKArray.merge(other) (gk:111-154), stream by stream, as the left fold
  * dst.merge(srcs[0]); dst.merge(srcs[1]); ...  Like the reference it mutates

@@ -710,6 +710,67 @@ int gk_stats_select(gk_set* h, const int32_t* ids, int64_t count, int64_t* n, do
   return GK_OK;
 }
 
+// ---- rank queries: bounds on each stream's count of values <= x (gk_capi.h)
+
+static int check_rank(const double* xs, int nx, const int64_t* lo, const int64_t* hi) {
+  if (nx < 0 || (nx > 0 && (!xs || (!lo && !hi)))) return fail(GK_E_ARG, "bad rank arguments");
+  for (int i = 0; i < nx; ++i)
+    if (std::isnan(xs[i])) return fail(GK_E_ARG, "xs[%d] is NaN", i);
+  return GK_OK;
+}
+
+// one row: the four rules of gk_capi.h on a flushed stream (read-only).  The
+// table is ascending: the walk stops at entry i, the first with v > x, holding
+// G(i) -- then G(i+1) + d_i - 1 = G(i) + g_i + d_i - 1.
+static void rank_row(const Stream& st, const double* xs, int nx, int64_t* lo, int64_t* hi) {
+  const int64_t E = (int64_t)st.tab.size();
+  for (int t = 0; t < nx; ++t) {
+    const double x = xs[t];
+    int64_t l, u;
+    if (st.n == 0 || x < st.mn) {
+      l = u = 0;
+    } else if (x >= st.mx) {
+      l = u = st.n;
+    } else {
+      int64_t i = 0, G = 0;
+      for (; i < E && st.tab[(size_t)i].v <= x; ++i) G += st.tab[(size_t)i].g;
+      l = std::max<int64_t>(G, 1);
+      u = std::min<int64_t>(i < E ? G + st.tab[(size_t)i].g + st.tab[(size_t)i].d - 1 : st.n, st.n - 1);
+    }
+    if (lo) lo[t] = l;
+    if (hi) hi[t] = u;
+  }
+}
+
+int gk_ranks(gk_set* h, const double* xs, int nx, int64_t* lo, int64_t* hi, void* stream) {
+  (void)stream;
+  int rc = check_set(h);
+  if (!rc) rc = check_rank(xs, nx, lo, hi);
+  if (rc || nx == 0) return rc;
+  parallel_for(h->S, h->threads, [&](int64_t s) {
+    Stream& st = h->st[s];
+    if (st.n > 0) flush_if_pending(h, st);  // gk:166-167
+    rank_row(st, xs, nx, lo ? lo + s * (int64_t)nx : nullptr, hi ? hi + s * (int64_t)nx : nullptr);
+  });
+  return GK_OK;
+}
+
+int gk_ranks_select(gk_set* h, const int32_t* ids, int64_t count, const double* xs, int nx, int64_t* lo, int64_t* hi,
+                    void* stream) {
+  (void)stream;
+  int rc = check_set(h);
+  if (!rc) rc = check_rank(xs, nx, lo, hi);
+  if (!rc) rc = check_select(h, ids, count);
+  if (rc || count == 0 || nx == 0) return rc;
+  rc = flush_selected(h, ids, count);
+  if (rc) return rc;
+  // (read-only from here: rows of a repeated stream may be answered in parallel)
+  parallel_for(count, h->threads, [&](int64_t k) {
+    rank_row(h->st[ids[k]], xs, nx, lo ? lo + k * (int64_t)nx : nullptr, hi ? hi + k * (int64_t)nx : nullptr);
+  });
+  return GK_OK;
+}
+
 int gk_merge(gk_set* dst, gk_set* const* srcs, int nsrcs, void* stream) {
   (void)stream;
   int rc = check_set(dst);

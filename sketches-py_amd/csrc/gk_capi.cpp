@@ -1668,6 +1668,8 @@ int gk_sync(gk_set* h, void* stream) {
   return rc ? rc : take_sticky(h);
 }
 
+static int stage_qs(gk_set* h, const double* qs, int nq, hipStream_t s);
+
 // quantile arguments -> device copy of qs and the effective mode
 static int prepare_query(gk_set* h, const double* qs, int nq, double* out, int mode, hipStream_t s, GKQuery* q) {
   if (nq < 0 || (nq > 0 && (!qs || !out))) return fail(GK_E_ARG, "bad quantile arguments");
@@ -1683,6 +1685,18 @@ static int prepare_query(gk_set* h, const double* qs, int nq, double* out, int m
         break;
       }
   }
+  int rc = stage_qs(h, qs, nq, s);
+  if (rc) return rc;
+  q->qs = nq ? h->d_qs : nullptr;
+  q->nq = nq;
+  q->out = out;
+  q->mode = eff_mode;
+  return GK_OK;
+}
+
+// nq host doubles (quantiles, or the thresholds of a rank query) into the
+// set's device copy d_qs
+static int stage_qs(gk_set* h, const double* qs, int nq, hipStream_t s) {
   // the previous call's copy out of h_qs (and its kernels' reads of d_qs,
   // ordered on the same stream) must not see the new values
   HIP_TRY(hipEventSynchronize(h->ev_qs));
@@ -1707,10 +1721,6 @@ static int prepare_query(gk_set* h, const double* qs, int nq, double* out, int m
     HIP_TRY(hipEventRecord(h->ev_qs, s));
     h->qs_n = nq;
   }
-  q->qs = nq ? h->d_qs : nullptr;
-  q->nq = nq;
-  q->out = out;
-  q->mode = eff_mode;
   return GK_OK;
 }
 
@@ -1939,6 +1949,53 @@ int gk_stats_select(gk_set* h, const int32_t* ids, int64_t count, int64_t* n, do
   HIP_TRY(gk_launch_select_stats(h->st, ids, count, o, s));
   HIP_TRY(hipStreamSynchronize(s));
   return GK_OK;
+}
+
+// ---- rank queries: bounds on each stream's count of values <= x (k_rank)
+
+static int check_rank_args(const double* xs, int nx, const int64_t* lo, const int64_t* hi) {
+  if (nx < 0 || (nx > 0 && (!xs || (!lo && !hi)))) return fail(GK_E_ARG, "bad rank arguments");
+  for (int i = 0; i < nx; ++i)
+    if (std::isnan(xs[i])) return fail(GK_E_ARG, "xs[%d] is NaN", i);
+  return GK_OK;
+}
+
+int gk_ranks(gk_set* h, const double* xs, int nx, int64_t* lo, int64_t* hi, void* stream) {
+  int rc = check_set(h);
+  if (!rc) rc = check_rank_args(xs, nx, lo, hi);
+  if (!rc) rc = gk_sync(h, stream);
+  if (rc || nx == 0 || h->S == 0) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  rc = stage_qs(h, xs, nx, s);  // (before the flush: its GK_E_NOMEM mutates nothing)
+  if (rc) return rc;
+  // gk_quantiles' flush (gk:166-167 / gk:197-198), settled: deferred streams
+  // are re-run and a stream that outgrew the last class is reported
+  rc = gk_flush(h, stream);
+  if (!rc) rc = gk_sync(h, stream);
+  if (rc) return rc;  // (GK_E_OVERFLOW: lo and hi are not written)
+  HIP_TRY(gk_launch_rank(h->st, nullptr, h->S, h->d_qs, nx, lo, hi, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return GK_OK;
+}
+
+int gk_ranks_select(gk_set* h, const int32_t* ids, int64_t count, const double* xs, int nx, int64_t* lo, int64_t* hi,
+                    void* stream) {
+  int rc = check_set(h);
+  if (!rc) rc = check_select_args(ids, count);
+  if (!rc) rc = check_rank_args(xs, nx, lo, hi);
+  if (!rc) rc = gk_sync(h, stream);
+  if (rc || count == 0) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* list = nullptr;
+  int64_t nflush = 0;
+  rc = select_begin(h, ids, count, true, stream, &list, &nflush);
+  if (rc || nx == 0) return rc;
+  rc = stage_qs(h, xs, nx, s);  // (before the flush, as in gk_quantiles_select)
+  if (rc) return rc;
+  rc = select_flush(h, list, nflush, s);
+  if (rc) return rc;  // (GK_E_OVERFLOW: lo and hi are not written)
+  HIP_TRY(gk_launch_rank(h->st, ids, count, h->d_qs, nx, lo, hi, s));
+  return select_end(h, s);
 }
 
 static int merge_self(gk_set* dst, hipStream_t s, void* stream);

@@ -17,6 +17,8 @@
 //                           the incoming list, general four-rule walk (gk:76-106)
 //   k_select_*   gk:156-232, 45-46, 21-29  a list of stream ids: id check + flush
 //                           list, wave per row query, reset, stats gather
+//   k_rank       (no gk line: the reference has no rank())  wave per row: bounds on
+//                           the count of values <= x from the flushed table
 //   k_export / k_import / k_reset: state movement
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -214,6 +216,13 @@ __device__ __forceinline__ int wave_sum_i32(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// lane l's int64 in every lane (two v_readlane; l wave-uniform)
+__device__ __forceinline__ int64_t gk_readlane_i64(int64_t v, int l) {
+  const int lo = __builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)v, l);
+  const int hi = __builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), l);
+  return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
 }
 
 // Ordering point for a ONE-WAVE workgroup.  The LDS executes a wave's
@@ -1647,6 +1656,86 @@ __device__ __attribute__((noinline)) void wave_quantiles(const double* __restric
       else if (i < E) r = tv[(i - 1) * SV];                    // gk:185 / gk:220
       else r = (qmode == 0) ? mx : tv[(E - 1) * SV];           // gk:229 / gk:185
       out[q] = r;
+    }
+  }
+}
+
+// ===========================================================================
+// Rank bounds of one stream from its flushed table (DESIGN.md section 5,
+// "k_rank"; the reference has no rank()): for every threshold x the pair
+//   n == 0 or x < _min : (0, 0)        x >= _max : (n, n)        otherwise
+//   lo = max(G(i), 1),  hi = min(i < E ? G(i+1) + d_i - 1 : n, n - 1)
+// with i = #{k : v_k <= x} and G(k) = g_0 + .. + g_{k-1}, all int64.
+// The table is ascending, so the entries with v_k <= x ARE the first i: G(i)
+// is the sum of g over them and G(i+1) + d_i - 1 = G(i) + g_i + d_i - 1.  Both
+// i and G(i) are order-free sums over the table: lane l takes entries l,
+// l + 64, ... (each wave access one coalesced run of records; no prefix scan)
+// and ONE pass serves RK thresholds held in registers (thresholds beyond RK:
+// one more pass per RK).  The lane that owns threshold u of the pass then
+// loads entry i (only if i < E: nothing past entry E-1 is read) and stores
+// the pair.  Comparisons are IEEE (-0.0 == 0.0, +-inf ordinary).  lo or hi
+// may be NULL.  Every lane of the wave must be active (DPP reductions).
+// ===========================================================================
+#define GK_RANK_RK 8
+template <int SV, int SI>
+__device__ __forceinline__ void wave_ranks(const double* __restrict__ tv, const int32_t* __restrict__ tg,
+                                                     const int32_t* __restrict__ td, int E, int64_t n, double mn,
+                                                     double mx, const double* __restrict__ xs, int nx,
+                                                     int64_t* __restrict__ lo, int64_t* __restrict__ hi, int lane) {
+  for (int t0 = 0; t0 < nx; t0 += GK_RANK_RK) {
+    const int nt = min(GK_RANK_RK, nx - t0);
+    int my_i = 0;
+    int64_t my_G = 0;
+    if (n != 0) {
+      double x[GK_RANK_RK];
+      int cnt[GK_RANK_RK];
+      int64_t gs[GK_RANK_RK];
+#pragma unroll
+      for (int u = 0; u < GK_RANK_RK; ++u) {
+        x[u] = xs[t0 + min(u, nt - 1)];  // (wave-uniform; the tail repeats the last threshold)
+        cnt[u] = 0;
+        gs[u] = 0;
+      }
+#pragma unroll 4
+      for (int j = lane; j < E; j += 64) {  // (long tables: four records per lane in flight)
+        const double v = tv[(int64_t)j * SV];
+        const int64_t g = tg[(int64_t)j * SI];
+#pragma unroll
+        for (int u = 0; u < GK_RANK_RK; ++u) {
+          const bool le = v <= x[u];
+          cnt[u] += le ? 1 : 0;
+          gs[u] += le ? g : 0;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < GK_RANK_RK; ++u) {
+        if (u < nt) {  // (wave-uniform)
+          const int i = __builtin_amdgcn_readlane((int)wave_incl_scan_u32((uint32_t)cnt[u], lane), 63);
+          const int64_t Gi = gk_readlane_i64(wave_incl_scan_i64(gs[u], lane), 63);
+          if (lane == u) {
+            my_i = i;
+            my_G = Gi;
+          }
+        }
+      }
+    }
+    if (lane < nt) {
+      const double x = xs[t0 + lane];
+      int64_t l, h;
+      if (n == 0 || x < mn) {
+        l = 0;
+        h = 0;
+      } else if (x >= mx) {
+        l = n;
+        h = n;
+      } else {
+        l = my_G > 1 ? my_G : 1;
+        int64_t up = n;
+        if (my_i < E) up = my_G + (int64_t)tg[(int64_t)my_i * SI] + (int64_t)td[(int64_t)my_i * SI] - 1;
+        h = up < n - 1 ? up : n - 1;
+      }
+      if (lo) lo[t0 + lane] = l;
+      if (hi) hi[t0 + lane] = h;
     }
   }
 }
@@ -5364,6 +5453,23 @@ __global__ __launch_bounds__(256) void k_select_query(GKState st, const int32_t*
   }
 }
 
+// k_rank: row k of lo / hi = the rank bounds (wave_ranks) of stream ids[k] --
+// ids == NULL: of stream k -- for the nx thresholds xs, from its committed
+// table, one wave per row.  The call has flushed and synchronised: the table
+// and n / _min / _max are final.  Reads only; lo or hi may be NULL.
+__global__ __launch_bounds__(256, 6) void k_rank(GKState st, const int32_t* __restrict__ ids, int64_t count,
+                                              const double* __restrict__ xs, int nx, int64_t* __restrict__ lo,
+                                              int64_t* __restrict__ hi) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wid = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwv = (int64_t)gridDim.x * 4;
+  for (int64_t k = wid; k < count; k += nwv) {
+    const int64_t s = ids ? (int64_t)ids[k] : k;
+    const GKRec* tab = gk_table_ptr(st, s);
+    wave_ranks<2, 4>(&tab->v, &tab->g, &tab->d, st.E[s], st.n[s], st.mn[s], st.mx[s], xs, nx,
+                     lo ? lo + k * (int64_t)nx : nullptr, hi ? hi + k * (int64_t)nx : nullptr, lane);
+  }
+}
+
 // k_select_reset: every listed stream back to GKArray(eps) (gk:21-29), the
 // header values of k_reset -- but cls and slot stay: arenas are bump-allocated
 // and the class member lists have no removal, so a stream put back in class 0
@@ -6053,6 +6159,13 @@ hipError_t gk_launch_select_query(const GKState& st, const int32_t* ids, int64_t
   if (count <= 0 || !q.qs || q.nq <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_select_query, dim3((unsigned)wave_grid(count)), dim3(256), 0, stream, st, ids, count, q.qs,
                      q.nq, q.mode, q.out);
+  return hipGetLastError();
+}
+
+hipError_t gk_launch_rank(const GKState& st, const int32_t* ids, int64_t count, const double* xs, int nx, int64_t* lo,
+                          int64_t* hi, hipStream_t stream) {
+  if (count <= 0 || !xs || nx <= 0 || (!lo && !hi)) return hipSuccess;
+  hipLaunchKernelGGL(k_rank, dim3((unsigned)wave_grid(count)), dim3(256), 0, stream, st, ids, count, xs, nx, lo, hi);
   return hipGetLastError();
 }
 

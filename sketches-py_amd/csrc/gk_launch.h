@@ -204,6 +204,11 @@ hipError_t gk_launch_select_check(const GKState& st, const int32_t* ids, int64_t
 // q.out[k * nq ..] = the quantiles of stream ids[k] from its committed table
 hipError_t gk_launch_select_query(const GKState& st, const int32_t* ids, int64_t count, const GKQuery& q,
                                   hipStream_t stream);
+// rank bounds (gk_ranks / gk_ranks_select): lo / hi[k * nx ..] = the bounds of
+// stream ids[k] (ids == NULL: of stream k, count == S) for the thresholds
+// xs[0 .. nx) (device), from its committed table; lo or hi may be NULL
+hipError_t gk_launch_rank(const GKState& st, const int32_t* ids, int64_t count, const double* xs, int nx, int64_t* lo,
+                          int64_t* hi, hipStream_t stream);
 // the listed streams back to empty sketches; class and slot stay as they are
 hipError_t gk_launch_select_reset(const GKState& st, const int32_t* ids, int64_t count, hipStream_t stream);
 // gk_stats' arrays gathered at ids (device arrays of `count` entries, any may be NULL)

@@ -253,6 +253,21 @@ class GKArray:
         out = self._set.quantiles([q], single=True)
         return np.float64(out[0, 0].item())
 
+    def rank(self, x):
+        """Extension (the reference has no rank()): ``(lo, hi)``, Python ints
+        with ``lo <= #{values <= x} <= hi`` for a sketch built by ``add``
+        alone (``StreamSet.ranks``).  Flushes pending values, as ``quantile``
+        does."""
+        self._ship()
+        lo, hi = self._set.ranks([float(x)])
+        return int(lo[0, 0].item()), int(hi[0, 0].item())
+
+    def cdf(self, x):
+        """Extension: the point estimate ``(lo + hi) / (2 n)`` of the share of
+        values <= x (``StreamSet.cdf``); NaN for an empty sketch."""
+        self._ship()
+        return float(self._set.cdf([float(x)])[0, 0].item())
+
     def quantiles(self, q_values):
         """gk:187-232."""
         st = self._stats()

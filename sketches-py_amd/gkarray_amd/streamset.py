@@ -397,6 +397,79 @@ class StreamSet:
         self._inflight = None
         return {k: v[:K] for k, v in d.items()}
 
+    # ------------------------------------------------------------ rank queries
+    def _rank_out(self, want, rows, nx, name):
+        """An output of ``ranks``: (tensor handed back, tensor whose pointer the
+        call gets) -- (None, None) for an output that is not wanted."""
+        if want is None or want is False:
+            return None, None
+        if want is True:
+            t = torch.empty((max(rows, 1), max(nx, 1)), dtype=torch.int64, device=self.device)
+            return t[:rows, :nx], t
+        if not isinstance(want, torch.Tensor) or want.dtype != torch.int64 or want.device != self.device \
+                or not want.is_contiguous() or tuple(want.shape) != (rows, nx):
+            raise ValueError("%s must be True, False or a contiguous int64 tensor of shape (%d, %d) on %s"
+                             % (name, rows, nx, self.device))
+        return want, (want if want.numel() else torch.empty(1, dtype=torch.int64, device=self.device))
+
+    def ranks(self, xs, lo=True, hi=True):
+        """Bounds on every stream's count of values <= x (``gk_ranks``), the
+        inverse of ``quantiles``: ``(lo, hi)``, int64 device tensors
+        [S, len(xs)] with ``lo <= #{values <= x} <= hi`` and ``hi - lo <=
+        2 eps n`` for a stream built by ``add`` alone (after a merge or a
+        roll-up the pair is still the formula on the table, gk_capi.h, but the
+        true count may lie outside).  Pending values are flushed first, as
+        ``quantiles`` does.  ``xs``: any order, repeats allowed, no NaN.
+        ``lo`` / ``hi``: False leaves that output out (None is returned in its
+        place); an int64 tensor [S, len(xs)] on the set's device is written in
+        place."""
+        xs = [float(x) for x in xs]
+        nx = len(xs)
+        S = self.num_streams
+        lo_t, lo_p = self._rank_out(lo, S, nx, "lo")
+        hi_t, hi_p = self._rank_out(hi, S, nx, "hi")
+        arr = (ctypes.c_double * max(nx, 1))(*xs)
+        with self._ctx():
+            try:
+                self._check(self._lib.gk_ranks(self._h, arr, nx, _ptr(lo_p), _ptr(hi_p), self._sp()))
+            finally:
+                self._inflight = None  # (the call synchronised)
+        return lo_t, hi_t
+
+    def ranks_select(self, ids, xs, lo=True, hi=True):
+        """``ranks(xs)`` of the listed streams (``gk_ranks_select``): int64
+        tensors [len(ids), len(xs)], row k for ``ids[k]``.  Only the listed
+        streams with pending values are flushed; ids as ``quantiles_select``."""
+        i = self._select_ids(ids)
+        K = i.numel()
+        xs = [float(x) for x in xs]
+        nx = len(xs)
+        lo_t, lo_p = self._rank_out(lo, K, nx, "lo")
+        hi_t, hi_p = self._rank_out(hi, K, nx, "hi")
+        arr = (ctypes.c_double * max(nx, 1))(*xs)
+        with self._ctx():
+            self._check(self._lib.gk_ranks_select(self._h, _ptr(i) if K else None, K, arr, nx, _ptr(lo_p), _ptr(hi_p),
+                                                  self._sp()))
+        self._inflight = None
+        return lo_t, hi_t
+
+    @staticmethod
+    def _cdf(lo, hi, n):
+        # (lo + hi) / (2 n); 0 / 0 = NaN where n == 0
+        return (lo + hi).to(torch.float64) / (2.0 * n.to(torch.float64)).unsqueeze(1)
+
+    def cdf(self, xs):
+        """Point estimate of every stream's share of values <= x: float64
+        [S, len(xs)], ``(lo + hi) / (2 n)`` of ``ranks(xs)``; NaN where n == 0."""
+        lo, hi = self.ranks(xs)
+        return self._cdf(lo, hi, self.stats()["n"])
+
+    def cdf_select(self, ids, xs):
+        """``cdf(xs)`` of the listed streams: float64 [len(ids), len(xs)]."""
+        i = self._select_ids(ids)
+        lo, hi = self.ranks_select(i, xs)
+        return self._cdf(lo, hi, self.stats_select(i)["n"])
+
     # ------------------------------------------------------------------ export
     def tables(self):
         """All tables in CSR form: (offs int64[S+1], v f64, g i32, d i32)."""
