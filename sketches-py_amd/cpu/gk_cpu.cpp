@@ -11,7 +11,6 @@
 // are evaluated exactly as written.
 #include <math.h>
 #include <sched.h>
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -28,22 +27,11 @@
 #include <vector>
 
 #include "gk_cpu.h"
+#include "gk_checks.h"
 #include "gk_format.h"
 #include "gk_pack.h"
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
 
 // one (v, g, delta) tuple of a table (gk:8-16)
 struct Rec {
@@ -349,19 +337,6 @@ void quantiles_list(const gk_set* h, const Stream& s, const double* qs, int nq, 
   for (; j < nq; ++j) out[j] = (qs[j] < 0 || qs[j] > 1) ? nan_value() : s.mx;  // gk:225-230
 }
 
-int check_set(const gk_set* h) {
-  if (!h) return fail(GK_E_ARG, "null set");
-  return GK_OK;
-}
-
-int check_query(const double* qs, int nq, double* out, int mode) {
-  if (nq < 0 || (nq > 0 && (!qs || !out))) return fail(GK_E_ARG, "bad quantile arguments");
-  if (mode != GK_Q_LIST && mode != GK_Q_SINGLE) return fail(GK_E_ARG, "bad mode %d", mode);
-  for (int i = 0; i < nq; ++i)
-    if (std::isnan(qs[i])) return fail(GK_E_ARG, "cannot convert float NaN to integer");
-  return GK_OK;
-}
-
 // gk:205: an unsorted list is answered q by q with quantile()
 int effective_mode(const double* qs, int nq, int mode) {
   if (mode == GK_Q_LIST)
@@ -505,7 +480,8 @@ int gk_ingest(gk_set* h, const double* values, const int64_t* offsets, void* str
 // in-order scatter.  A bad id (>= S) leaves out_offsets all zero.
 static int group_impl(const gk_set* h, const int32_t* ids, const double* values, int64_t count, double* out_values,
                       int64_t* out_offsets) {
-  if (count < 0 || count > INT32_MAX) return fail(GK_E_ARG, "count %lld outside [0, 2^31-1]", (long long)count);
+  int rc = check_count(count);
+  if (rc) return rc;
   if (!out_offsets) return fail(GK_E_ARG, "out_offsets is null");
   if (count > 0 && (!ids || !values || !out_values)) return fail(GK_E_ARG, "ids, values or out_values is null");
   const int64_t S = h->S;
@@ -541,9 +517,9 @@ int gk_group_by_key(gk_set* h, const int32_t* ids, const double* values, int64_t
 int gk_ingest_keyed(gk_set* h, const int32_t* ids, const double* values, int64_t count, const double* qs, int nq,
                     double* out, int mode, void* stream) {
   int rc = check_set(h);
-  if (!rc) rc = check_query(qs, nq, out, mode);
+  if (!rc) rc = check_query_args(qs, nq, out, mode);
+  if (!rc) rc = check_count(count);
   if (rc) return rc;
-  if (count < 0 || count > INT32_MAX) return fail(GK_E_ARG, "count %lld outside [0, 2^31-1]", (long long)count);
   if (h->S == 0) return GK_OK;
   try {
     if ((int64_t)h->key_vals.size() < std::max<int64_t>(count, 1)) h->key_vals.resize((size_t)std::max<int64_t>(count, 1));
@@ -574,7 +550,7 @@ int gk_sync(gk_set* h, void* stream) {
 int gk_quantiles(gk_set* h, const double* qs, int nq, double* out, int mode, void* stream) {
   (void)stream;
   int rc = check_set(h);
-  if (!rc) rc = check_query(qs, nq, out, mode);
+  if (!rc) rc = check_query_args(qs, nq, out, mode);
   if (rc) return rc;
   if (nq == 0) return GK_OK;
   mode = effective_mode(qs, nq, mode);
@@ -590,7 +566,7 @@ int gk_ingest_quantiles(gk_set* h, const double* values, const int64_t* offsets,
                         double* out, int mode, void* stream) {
   (void)stream;
   int rc = check_set(h);
-  if (!rc) rc = check_query(qs, nq, out, mode);
+  if (!rc) rc = check_query_args(qs, nq, out, mode);
   if (rc) return rc;
   if (nq == 0) return ingest_impl(h, values, offsets, nullptr, 0, nullptr, mode);
   return ingest_impl(h, values, offsets, qs, nq, out, effective_mode(qs, nq, mode));
@@ -618,8 +594,8 @@ int gk_stats(gk_set* h, int64_t* n, double* mn, double* mx, double* sum, double*
 
 // count and ids checked (every id in [0, S)) before anything is mutated
 static int check_select(const gk_set* h, const int32_t* ids, int64_t count) {
-  if (count < 0 || count > INT32_MAX) return fail(GK_E_ARG, "count %lld outside [0, 2^31-1]", (long long)count);
-  if (count > 0 && !ids) return fail(GK_E_ARG, "ids is null");
+  int rc = check_select_args(ids, count);
+  if (rc) return rc;
   for (int64_t k = 0; k < count; ++k)
     if (ids[k] < 0 || ids[k] >= h->S)
       return fail(GK_E_ARG, "ids[%lld] = %d lies outside [0, %lld)", (long long)k, ids[k], (long long)h->S);
@@ -667,7 +643,7 @@ int gk_quantiles_select(gk_set* h, const int32_t* ids, int64_t count, const doub
                         void* stream) {
   (void)stream;
   int rc = check_set(h);
-  if (!rc) rc = check_query(qs, nq, out, mode);
+  if (!rc) rc = check_query_args(qs, nq, out, mode);
   if (!rc) rc = check_select(h, ids, count);
   if (rc || count == 0 || nq == 0) return rc;
   mode = effective_mode(qs, nq, mode);
@@ -712,13 +688,6 @@ int gk_stats_select(gk_set* h, const int32_t* ids, int64_t count, int64_t* n, do
 
 // ---- rank queries: bounds on each stream's count of values <= x (gk_capi.h)
 
-static int check_rank(const double* xs, int nx, const int64_t* lo, const int64_t* hi) {
-  if (nx < 0 || (nx > 0 && (!xs || (!lo && !hi)))) return fail(GK_E_ARG, "bad rank arguments");
-  for (int i = 0; i < nx; ++i)
-    if (std::isnan(xs[i])) return fail(GK_E_ARG, "xs[%d] is NaN", i);
-  return GK_OK;
-}
-
 // one row: the four rules of gk_capi.h on a flushed stream (read-only).  The
 // table is ascending: the walk stops at entry i, the first with v > x, holding
 // G(i) -- then G(i+1) + d_i - 1 = G(i) + g_i + d_i - 1.
@@ -745,7 +714,7 @@ static void rank_row(const Stream& st, const double* xs, int nx, int64_t* lo, in
 int gk_ranks(gk_set* h, const double* xs, int nx, int64_t* lo, int64_t* hi, void* stream) {
   (void)stream;
   int rc = check_set(h);
-  if (!rc) rc = check_rank(xs, nx, lo, hi);
+  if (!rc) rc = check_rank_args(xs, nx, lo, hi);
   if (rc || nx == 0) return rc;
   parallel_for(h->S, h->threads, [&](int64_t s) {
     Stream& st = h->st[s];
@@ -759,7 +728,7 @@ int gk_ranks_select(gk_set* h, const int32_t* ids, int64_t count, const double* 
                     void* stream) {
   (void)stream;
   int rc = check_set(h);
-  if (!rc) rc = check_rank(xs, nx, lo, hi);
+  if (!rc) rc = check_rank_args(xs, nx, lo, hi);
   if (!rc) rc = check_select(h, ids, count);
   if (rc || count == 0 || nx == 0) return rc;
   rc = flush_selected(h, ids, count);
@@ -773,16 +742,8 @@ int gk_ranks_select(gk_set* h, const int32_t* ids, int64_t count, const double* 
 
 int gk_merge(gk_set* dst, gk_set* const* srcs, int nsrcs, void* stream) {
   (void)stream;
-  int rc = check_set(dst);
+  int rc = check_merge_args(dst, srcs, nsrcs);
   if (rc) return rc;
-  if (nsrcs < 0 || (nsrcs > 0 && !srcs)) return fail(GK_E_ARG, "bad source list");
-  for (int k = 0; k < nsrcs; ++k) {
-    if (!srcs[k]) return fail(GK_E_ARG, "null source %d", k);
-    if (srcs[k]->eps != dst->eps)  // gk:118-119
-      return fail(GK_E_EPS_MISMATCH, "Cannot merge two GKArrays with different epsilon values");
-    if (srcs[k]->S != dst->S)
-      return fail(GK_E_ARG, "stream counts differ (%lld vs %lld)", (long long)srcs[k]->S, (long long)dst->S);
-  }
   // the fold runs per stream: dst.merge(srcs[0]); dst.merge(srcs[1]); ...
   // A source may be dst itself (gk:111-154 accepts other is self: the flush
   // of gk:137 empties dst's own incoming, the conversion reads the flushed
@@ -797,13 +758,8 @@ int gk_merge(gk_set* dst, gk_set* const* srcs, int nsrcs, void* stream) {
 
 int gk_rollup(gk_set* dst, gk_set* src, const int64_t* group_offsets, const int64_t* members, void* stream) {
   (void)stream;
-  int rc = check_set(dst);
-  if (!rc) rc = check_set(src);
+  int rc = check_rollup_args(dst, src, group_offsets);
   if (rc) return rc;
-  if (dst == src) return fail(GK_E_ARG, "roll-up of a set into itself");
-  if (!group_offsets) return fail(GK_E_ARG, "group_offsets is null");
-  if (src->eps != dst->eps)  // gk:118-119
-    return fail(GK_E_EPS_MISMATCH, "Cannot merge two GKArrays with different epsilon values");
   const int64_t G = dst->S, S = src->S;
   if (group_offsets[0] != 0) return fail(GK_E_ARG, "group_offsets must start at 0");
   for (int64_t j = 0; j < G; ++j)
@@ -834,8 +790,8 @@ int gk_merge_compress(gk_set* h, const double* v, const int32_t* g, const int32_
                       void* stream) {
   (void)stream;
   int rc = check_set(h);
+  if (!rc) rc = check_record_args(v, g, d, eoffs);
   if (rc) return rc;
-  if (!eoffs || !v || !g || !d) return fail(GK_E_ARG, "null record arrays");
   parallel_for(h->S, h->threads, [&](int64_t s) {
     std::vector<Rec> recs;
     for (int64_t k = eoffs[s]; k < eoffs[s + 1]; ++k) recs.push_back(Rec{v[k], g[k], d[k]});

@@ -12,18 +12,19 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "gk_capi.h"
+#include "gk_checks.h"
 #include "gk_pack.h"
 #include "gk_format.h"
 #include "gk_launch.h"
@@ -31,18 +32,6 @@
 #include "gk_host_stats.h"
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
 
 #define HIP_TRY(expr)                                                                  \
   do {                                                                                 \
@@ -59,6 +48,19 @@ constexpr int kPMax = 1 << 24;    // largest flush period (eps >= 6e-8)
 constexpr int64_t kRecipTable = (int64_t)1 << 17;  // entries of st.rtab (1 MiB)
 constexpr int kMaxLdsCap = 2048;
 constexpr int kRounds = GK_MAX_CLASSES + 1;  // overflow lists: launch round 0 + one per promotion level
+
+// Renew a device buffer: the old one is freed (the caller has synchronised
+// whatever may still use it) and `bytes` are allocated in its place.  On
+// failure *p is null and the HIP error is cleared.
+template <typename T>
+bool renew_dev(T** p, size_t bytes) {
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  if (hipMalloc((void**)p, bytes) == hipSuccess) return true;
+  *p = nullptr;
+  (void)hipGetLastError();
+  return false;
+}
 
 int vpl_for(int P) {
   int v = 1;
@@ -492,15 +494,8 @@ int grow_pools(gk_set* h, hipStream_t s) {
     HIP_TRY(hipStreamSynchronize(h->aux));
     if (h->aux2) HIP_TRY(hipStreamSynchronize(h->aux2));
     if (h->aux3) HIP_TRY(hipStreamSynchronize(h->aux3));
-    if (h->ps.ws) (void)hipFree(h->ps.ws);
-    h->ps.ws = nullptr;
-    h->ps.ws_cap = 0;
-    if (hipMalloc(&h->ps.ws, (size_t)cap * sizeof(double)) == hipSuccess) {
-      h->ps.ws_cap = cap;
-    } else {
-      h->ps.ws = nullptr;  // not fatal: long streams flush unsorted
-      (void)hipGetLastError();
-    }
+    // (a failure is not fatal: long streams flush unsorted)
+    h->ps.ws_cap = renew_dev(&h->ps.ws, (size_t)cap * sizeof(double)) ? cap : 0;
   }
   return GK_OK;
 }
@@ -542,11 +537,6 @@ int64_t read_overflow(gk_set* h, int r, hipStream_t stream) {
       hipStreamSynchronize(stream) != hipSuccess)
     return fail(GK_E_HIP, "overflow readback failed: %s", hipGetErrorString(hipGetLastError()));
   return h->h_ovf[0];
-}
-
-int check_set(const gk_set* h) {
-  if (!h) return fail(GK_E_ARG, "null set");
-  return GK_OK;
 }
 
 hipEvent_t timing_event(std::vector<hipEvent_t>& v, size_t& n) {
@@ -1103,12 +1093,18 @@ int run_ingest(gk_set* h, const double* x, const int64_t* offs, int force, hipSt
   return promote_rounds(h, x, offs, force, q, stream, fresh);
 }
 
-// Merge / explicit merge_compress at LDS capacity level 0, then the streams
-// that did not fit at increasing levels (their class raised on the device).
-// Synchronous (one readback per level).  base.list / base.count (optional):
-// only these streams instead of every stream.
-int run_merge(gk_set* dst, const MergeArgsHost& base, hipStream_t s) {
-  MergeArgsHost a = base;
+// The capacity-level ladder of the synchronous folds (merge, merge_compress,
+// roll-up): `launch` runs at level 0 over every stream of dst, then at each
+// further level over the streams that did not fit the level before -- their
+// class is raised on the device first (the arena grown for them), so that
+// their output may grow.  One overflow readback per level.
+// launch(level, cap, list, count, ovf_count, ovf_list, ws, ws_bytes,
+// ws_blocks) -> hipError_t: list is NULL at level 0 (count = dst->S), ws NULL
+// for an LDS capacity; it reads dst->st at the call (the arenas move).
+// overflow_fmt: the GK_E_OVERFLOW message past the last level, taking the
+// stream count (%lld) and the largest capacity (%d).
+template <typename Launch>
+int run_levels(gk_set* dst, hipStream_t s, Launch&& launch, const char* overflow_fmt) {
   const GKPoolDev pool = pool_args(dst);
   int64_t todo = 0;
   dst->ctr_clean = false;
@@ -1117,93 +1113,104 @@ int run_merge(gk_set* dst, const MergeArgsHost& base, hipStream_t s) {
     const int cap = dst->st.cap[level];
     if (level > 0) {
       if (todo == 0) return GK_OK;
-      // streams below this class move up so that their output may grow
       int rc = grow_class(dst, level, (int64_t)dst->st.alloc[level] + todo, s);
       if (rc) return rc;
       dst->no_members = false;
       HIP_TRY(gk_launch_promote_dev(dst->st, ovf_count(dst, level - 1), ovf_list(dst, level - 1), level, pool, s));
     }
-    a.dst = dst->st;
-    a.cap = cap;
-    a.list = level == 0 ? base.list : ovf_list(dst, level - 1);
-    a.count = level == 0 ? (base.list ? base.count : dst->S) : todo;
-    a.ovf_count = ovf_count(dst, level);
-    a.ovf_list = ovf_list(dst, level);
-    if (cap > kMaxLdsCap) {
+    const bool lds = cap <= kMaxLdsCap;
+    if (!lds) {
       int rc = ensure_ws(dst, level);
       if (rc) return rc;
-      a.ws = dst->d_ws[level];
-      a.ws_bytes = dst->ws_bytes[level];
-      a.ws_blocks = dst->ws_blocks[level];
-    } else {
-      a.ws = nullptr;
-      a.ws_bytes = 0;
-      a.ws_blocks = 0;
     }
-    HIP_TRY(gk_launch_merge(a, s));
+    HIP_TRY(launch(level, cap, level == 0 ? nullptr : ovf_list(dst, level - 1), level == 0 ? dst->S : todo,
+                   ovf_count(dst, level), ovf_list(dst, level), lds ? nullptr : dst->d_ws[level],
+                   lds ? 0 : dst->ws_bytes[level], lds ? 0 : dst->ws_blocks[level]));
     todo = read_overflow(dst, level, s);
     if (todo < 0) return (int)todo;
     if (todo == 0) return GK_OK;
   }
-  return fail(GK_E_OVERFLOW, "%lld stream(s) exceed %d table entries in merge, or the per-stream count limit "
-              "2*eps*(n-1) <= 2^30", (long long)todo, dst->st.cap[dst->st.nclass - 1]);
+  return fail(GK_E_OVERFLOW, overflow_fmt, (long long)todo, dst->st.cap[dst->st.nclass - 1]);
 }
 
-// The roll-up fold (k_rollup) at capacity level 0, then the destinations whose
-// fold stopped at a member that did not fit, at increasing levels: their class
-// is raised and the fold resumes at the recorded member (run_merge's scheme).
-// Synchronous (one readback per level).
+// The per-level fields of a fold's argument struct (MergeArgsHost / RollupArgsHost)
+template <typename Args>
+void set_level(Args& a, const GKState& dst, int cap, const int32_t* list, int64_t count, int32_t* ovf_count,
+               int32_t* ovf_list, unsigned char* ws, size_t ws_bytes, int64_t ws_blocks) {
+  a.dst = dst;
+  a.cap = cap;
+  a.list = list;
+  a.count = count;
+  a.ovf_count = ovf_count;
+  a.ovf_list = ovf_list;
+  a.ws = ws;
+  a.ws_bytes = ws_bytes;
+  a.ws_blocks = ws_blocks;
+}
+
+// Merge / explicit merge_compress up the ladder.  base.list / base.count
+// (optional): only these streams at level 0 instead of every stream.
+int run_merge(gk_set* dst, const MergeArgsHost& base, hipStream_t s) {
+  MergeArgsHost a = base;
+  return run_levels(
+      dst, s,
+      [&](int level, int cap, const int32_t* list, int64_t count, int32_t* ovf_count, int32_t* ovf_list,
+          unsigned char* ws, size_t ws_bytes, int64_t ws_blocks) {
+        set_level(a, dst->st, cap, list, count, ovf_count, ovf_list, ws, ws_bytes, ws_blocks);
+        if (level == 0 && base.list) {
+          a.list = base.list;
+          a.count = base.count;
+        }
+        return gk_launch_merge(a, s);
+      },
+      "%lld stream(s) exceed %d table entries in merge, or the per-stream count limit "
+      "2*eps*(n-1) <= 2^30");
+}
+
+// The roll-up fold (k_rollup) up the ladder: a destination whose fold stopped
+// at a member that did not fit resumes at the recorded member one level up.
 int run_rollup(gk_set* dst, const gk_set* src, const int64_t* goffs, const int64_t* members, hipStream_t s) {
-  if (!dst->d_roll_prog &&
-      hipMalloc(&dst->d_roll_prog, (size_t)std::max<int64_t>(dst->S, 1) * sizeof(int64_t)) != hipSuccess) {
-    dst->d_roll_prog = nullptr;
+  if (!dst->d_roll_prog && !renew_dev(&dst->d_roll_prog, (size_t)std::max<int64_t>(dst->S, 1) * sizeof(int64_t)))
     return fail(GK_E_NOMEM, "roll-up progress array of %lld entries failed", (long long)dst->S);
-  }
   RollupArgsHost a{};
   a.src = src->st;
   a.goffs = goffs;
   a.members = members;
   a.progress = dst->d_roll_prog;
-  const GKPoolDev pool = pool_args(dst);
-  int64_t todo = 0;
-  dst->ctr_clean = false;
-  HIP_TRY(hipMemsetAsync(dst->d_ovfc, 0, kRounds * sizeof(int32_t), s));
-  for (int level = 0; level < dst->st.nclass; ++level) {
-    const int cap = dst->st.cap[level];
-    if (level > 0) {
-      if (todo == 0) return GK_OK;
-      // destinations below this class move up so that their fold may go on
-      int rc = grow_class(dst, level, (int64_t)dst->st.alloc[level] + todo, s);
-      if (rc) return rc;
-      dst->no_members = false;
-      HIP_TRY(gk_launch_promote_dev(dst->st, ovf_count(dst, level - 1), ovf_list(dst, level - 1), level, pool, s));
-    }
-    a.dst = dst->st;
-    a.cap = cap;
-    a.resume = level > 0;
-    a.list = level == 0 ? nullptr : ovf_list(dst, level - 1);
-    a.count = level == 0 ? dst->S : todo;
-    a.ovf_count = ovf_count(dst, level);
-    a.ovf_list = ovf_list(dst, level);
-    if (cap > kMaxLdsCap) {
-      int rc = ensure_ws(dst, level);
-      if (rc) return rc;
-      a.ws = dst->d_ws[level];
-      a.ws_bytes = dst->ws_bytes[level];
-      a.ws_blocks = dst->ws_blocks[level];
-    } else {
-      a.ws = nullptr;
-      a.ws_bytes = 0;
-      a.ws_blocks = 0;
-    }
-    HIP_TRY(gk_launch_rollup(a, s));
-    todo = read_overflow(dst, level, s);
-    if (todo < 0) return (int)todo;
-    if (todo == 0) return GK_OK;
-  }
-  return fail(GK_E_OVERFLOW, "%lld destination stream(s) exceed %d table entries in roll-up, or the per-stream count "
-              "limit 2*eps*(n-1) <= 2^30: they hold the fold of the members before the one that did not fit",
-              (long long)todo, dst->st.cap[dst->st.nclass - 1]);
+  return run_levels(
+      dst, s,
+      [&](int level, int cap, const int32_t* list, int64_t count, int32_t* ovf_count, int32_t* ovf_list,
+          unsigned char* ws, size_t ws_bytes, int64_t ws_blocks) {
+        set_level(a, dst->st, cap, list, count, ovf_count, ovf_list, ws, ws_bytes, ws_blocks);
+        a.resume = level > 0;
+        return gk_launch_rollup(a, s);
+      },
+      "%lld destination stream(s) exceed %d table entries in roll-up, or the per-stream count "
+      "limit 2*eps*(n-1) <= 2^30: they hold the fold of the members before the one that did not fit");
+}
+
+// k_merge's explicit-record mode with no records over the n streams of `list`
+// (device): merge_compress() of each; a stream that needs a larger class for
+// it climbs the ladder.
+int flush_listed(gk_set* h, const int32_t* list, int64_t n, hipStream_t s) {
+  if (n <= 0) return GK_OK;
+  MergeArgsHost a{};
+  a.src = h->st;
+  a.eoffs = h->d_zero_offs;
+  a.mode = 1;
+  a.list = list;
+  a.count = n;
+  return run_merge(h, a, s);
+}
+
+// other.merge_compress() of every stream of a fold's source -- unconditional
+// in the reference (gk:126, 137) -- as one batch flush, settled on return.
+int flush_source(gk_set* src, hipStream_t s, void* stream) {
+  int rc = begin_call(src, s);
+  if (!rc) rc = run_ingest(src, nullptr, nullptr, 2, s);
+  if (!rc) rc = mark_done(src, s);
+  if (!rc) rc = gk_sync(src, stream);
+  return rc;
 }
 
 }  // namespace
@@ -1541,18 +1548,10 @@ static int ensure_group_scratch(gk_set* h, int64_t count, bool grouped, hipStrea
              grow_sums = sums > h->kg_sums, grow_vals = grouped && (n > h->kg_vals_cap || !h->kg_offs);
   if (!(first || grow_pairs || grow_hist || grow_sums || grow_vals)) return GK_OK;
   HIP_TRY(hipStreamSynchronize(s));
-  auto renew = [](auto** p, size_t bytes) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    if (hipMalloc((void**)p, bytes) == hipSuccess) return true;
-    *p = nullptr;
-    (void)hipGetLastError();
-    return false;
-  };
   bool ok = true;
   if (first) {
     // per-call words and, behind them, the cumulative block: one allocation
-    ok = renew(&h->kg.call, (GK_KG_CALL_WORDS + GK_KG_CUM_WORDS) * sizeof(unsigned long long)) &&
+    ok = renew_dev(&h->kg.call, (GK_KG_CALL_WORDS + GK_KG_CUM_WORDS) * sizeof(unsigned long long)) &&
          hipMemset(h->kg.call, 0, (GK_KG_CALL_WORDS + GK_KG_CUM_WORDS) * sizeof(unsigned long long)) == hipSuccess &&
          hipHostMalloc(&h->h_kg, GK_KG_CUM_WORDS * sizeof(unsigned long long)) == hipSuccess;
     if (ok) {
@@ -1568,8 +1567,8 @@ static int ensure_group_scratch(gk_set* h, int64_t count, bool grouped, hipStrea
     h->kg_cap = 0;
     h->kg_pairs = 0;
     for (int k = 0; k < 2 && ok; ++k) {
-      if (k < pairs) ok = renew(&h->kg.ids[k], (size_t)cap * sizeof(int32_t));
-      if (ok && k < vbufs) ok = renew(&h->kg.vals[k], (size_t)cap * sizeof(double));
+      if (k < pairs) ok = renew_dev(&h->kg.ids[k], (size_t)cap * sizeof(int32_t));
+      if (ok && k < vbufs) ok = renew_dev(&h->kg.vals[k], (size_t)cap * sizeof(double));
     }
     if (ok) {
       h->kg_cap = cap;
@@ -1578,19 +1577,19 @@ static int ensure_group_scratch(gk_set* h, int64_t count, bool grouped, hipStrea
   }
   if (ok && grow_hist) {
     h->kg_tiles = 0;
-    ok = renew(&h->kg.hist, ((size_t)tiles << GK_GROUP_BITS) * sizeof(uint32_t));
+    ok = renew_dev(&h->kg.hist, ((size_t)tiles << GK_GROUP_BITS) * sizeof(uint32_t));
     if (ok) h->kg_tiles = tiles;
   }
   if (ok && grow_sums) {
     h->kg_sums = 0;
-    ok = renew(&h->kg.sums, (size_t)sums * sizeof(unsigned long long));
+    ok = renew_dev(&h->kg.sums, (size_t)sums * sizeof(unsigned long long));
     if (ok) h->kg_sums = sums;
   }
   if (ok && grow_vals) {
     const int64_t cap = std::max(n, h->kg_vals_cap);
     h->kg_vals_cap = 0;
-    ok = renew(&h->kg_vals, (size_t)cap * sizeof(double)) &&
-         (h->kg_offs || renew(&h->kg_offs, (size_t)(h->S + 1) * sizeof(int64_t)));
+    ok = renew_dev(&h->kg_vals, (size_t)cap * sizeof(double)) &&
+         (h->kg_offs || renew_dev(&h->kg_offs, (size_t)(h->S + 1) * sizeof(int64_t)));
     if (ok) h->kg_vals_cap = cap;
   }
   if (!ok) return fail(GK_E_NOMEM, "grouping scratch for %lld samples failed", (long long)count);
@@ -1598,7 +1597,8 @@ static int ensure_group_scratch(gk_set* h, int64_t count, bool grouped, hipStrea
 }
 
 static int check_keyed_args(const int32_t* ids, const double* values, int64_t count) {
-  if (count < 0 || count > INT32_MAX) return fail(GK_E_ARG, "count %lld outside [0, 2^31-1]", (long long)count);
+  int rc = check_count(count);
+  if (rc) return rc;
   if (count > 0 && (!ids || !values)) return fail(GK_E_ARG, "ids or values is null");
   return GK_OK;
 }
@@ -1622,13 +1622,8 @@ int gk_group_by_key(gk_set* h, const int32_t* ids, const double* values, int64_t
 int gk_ingest_keyed(gk_set* h, const int32_t* ids, const double* values, int64_t count, const double* qs, int nq,
                     double* out, int mode, void* stream) {
   int rc = check_set(h);
-  if (rc) return rc;
-  // (the checks of prepare_query, ahead of the grouping)
-  if (nq < 0 || (nq > 0 && (!qs || !out))) return fail(GK_E_ARG, "bad quantile arguments");
-  if (mode != GK_Q_LIST && mode != GK_Q_SINGLE) return fail(GK_E_ARG, "bad mode %d", mode);
-  for (int i = 0; i < nq; ++i)
-    if (std::isnan(qs[i])) return fail(GK_E_ARG, "cannot convert float NaN to integer");
-  rc = check_keyed_args(ids, values, count);
+  if (!rc) rc = check_query_args(qs, nq, out, mode);  // (ahead of the grouping)
+  if (!rc) rc = check_keyed_args(ids, values, count);
   if (rc) return rc;
   if (h->S == 0) return GK_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -1672,10 +1667,8 @@ static int stage_qs(gk_set* h, const double* qs, int nq, hipStream_t s);
 
 // quantile arguments -> device copy of qs and the effective mode
 static int prepare_query(gk_set* h, const double* qs, int nq, double* out, int mode, hipStream_t s, GKQuery* q) {
-  if (nq < 0 || (nq > 0 && (!qs || !out))) return fail(GK_E_ARG, "bad quantile arguments");
-  if (mode != GK_Q_LIST && mode != GK_Q_SINGLE) return fail(GK_E_ARG, "bad mode %d", mode);
-  for (int i = 0; i < nq; ++i)
-    if (std::isnan(qs[i])) return fail(GK_E_ARG, "cannot convert float NaN to integer");
+  int rc = check_query_args(qs, nq, out, mode);
+  if (rc) return rc;
   // gk:205-206: an unsorted list is answered q by q with quantile()
   int eff_mode = mode;
   if (mode == GK_Q_LIST) {
@@ -1685,7 +1678,7 @@ static int prepare_query(gk_set* h, const double* qs, int nq, double* out, int m
         break;
       }
   }
-  int rc = stage_qs(h, qs, nq, s);
+  rc = stage_qs(h, qs, nq, s);
   if (rc) return rc;
   q->qs = nq ? h->d_qs : nullptr;
   q->nq = nq;
@@ -1702,13 +1695,10 @@ static int stage_qs(gk_set* h, const double* qs, int nq, hipStream_t s) {
   HIP_TRY(hipEventSynchronize(h->ev_qs));
   if (nq > h->qs_alloc) {
     HIP_TRY(hipStreamSynchronize(s));
-    if (h->d_qs) (void)hipFree(h->d_qs);
     if (h->h_qs) (void)hipHostFree(h->h_qs);
-    h->d_qs = nullptr;
     h->h_qs = nullptr;
     const int cap = std::max(nq, 64);
-    if (hipMalloc(&h->d_qs, cap * sizeof(double)) != hipSuccess ||
-        hipHostMalloc(&h->h_qs, cap * sizeof(double)) != hipSuccess)
+    if (!renew_dev(&h->d_qs, cap * sizeof(double)) || hipHostMalloc(&h->h_qs, cap * sizeof(double)) != hipSuccess)
       return fail(GK_E_NOMEM, "qs allocation failed");
     h->qs_alloc = cap;
     h->qs_n = 0;
@@ -1797,12 +1787,6 @@ int gk_stats(gk_set* h, int64_t* n, double* mn, double* mx, double* sum, double*
 
 // ---- per-stream selection: query, flush, reset and stats of a list of streams
 
-static int check_select_args(const int32_t* ids, int64_t count) {
-  if (count < 0 || count > INT32_MAX) return fail(GK_E_ARG, "count %lld outside [0, 2^31-1]", (long long)count);
-  if (count > 0 && !ids) return fail(GK_E_ARG, "ids is null");
-  return GK_OK;
-}
-
 static int64_t select_bitmap_words(const gk_set* h, bool want_list) { return want_list ? (h->S + 31) / 32 : 0; }
 
 // The selection scratch: k_select_check's control words, then (want_list) the
@@ -1812,33 +1796,41 @@ static int ensure_select_scratch(gk_set* h, int64_t count, bool want_list) {
   const int64_t words =
       GK_SEL_WORDS + select_bitmap_words(h, want_list) + (want_list ? std::min<int64_t>(count, h->S) : 0);
   if (words <= h->sel_words) return GK_OK;
-  if (h->d_sel) (void)hipFree(h->d_sel);
-  h->d_sel = nullptr;
   h->sel_words = 0;
-  if (hipMalloc(&h->d_sel, (size_t)words * sizeof(int32_t)) != hipSuccess) {
-    h->d_sel = nullptr;
-    (void)hipGetLastError();
+  if (!renew_dev(&h->d_sel, (size_t)words * sizeof(int32_t)))
     return fail(GK_E_NOMEM, "selection scratch of %lld words failed", (long long)words);
-  }
   h->sel_words = words;
   return GK_OK;
 }
 
-// Head of every selection call, count > 0: the set's earlier work is settled
-// (gk_sync: deferred streams re-run, sticky errors returned), then ONE kernel
+// what select_begin found: the listed streams with n > 0 and pending values (device; want_list)
+struct Selection {
+  int32_t* list = nullptr;
+  int64_t nflush = 0;
+};
+
+// Head of every selection call: the set and the id list are checked, then the
+// call's other arguments (`more`, if any); the set's earlier work is settled (gk_sync:
+// deferred streams re-run, sticky errors returned); and, count > 0, ONE kernel
 // over ids checks their range and (want_list) lists the streams to flush --
-// nothing is mutated before its verdict has been read back.
-static int select_begin(gk_set* h, const int32_t* ids, int64_t count, bool want_list, void* stream, int32_t** list,
-                        int64_t* nflush) {
+// nothing is mutated before its verdict has been read back.  The caller
+// returns at once on an error or count == 0.
+static int select_begin(gk_set* h, const int32_t* ids, int64_t count, bool want_list, void* stream, Selection* sel,
+                        const std::function<int()>& more = nullptr) {
+  int rc = check_set(h);
+  if (!rc) rc = check_select_args(ids, count);
+  if (!rc && more) rc = more();
+  if (!rc) rc = gk_sync(h, stream);
+  if (rc || count == 0) return rc;
   hipStream_t s = (hipStream_t)stream;
-  int rc = ensure_select_scratch(h, count, want_list);
+  rc = ensure_select_scratch(h, count, want_list);
   if (rc) return rc;
   const int64_t bm = select_bitmap_words(h, want_list);
   int32_t* const ctl = h->d_sel;
   uint32_t* const bitmap = reinterpret_cast<uint32_t*>(ctl + GK_SEL_WORDS);
-  *list = want_list ? ctl + GK_SEL_WORDS + bm : nullptr;
+  sel->list = want_list ? ctl + GK_SEL_WORDS + bm : nullptr;
   HIP_TRY(hipMemsetAsync(ctl, 0, (size_t)(GK_SEL_WORDS + bm) * sizeof(int32_t), s));
-  HIP_TRY(gk_launch_select_check(h->st, ids, count, ctl, bitmap, *list, s));
+  HIP_TRY(gk_launch_select_check(h->st, ids, count, ctl, bitmap, sel->list, s));
   HIP_TRY(hipMemcpyAsync(h->h_ovf, ctl, GK_SEL_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   if (h->h_ovf[GK_SEL_BAD]) {
@@ -1847,22 +1839,8 @@ static int select_begin(gk_set* h, const int32_t* ids, int64_t count, bool want_
     HIP_TRY(hipMemcpy(&id, ids + first, sizeof(int32_t), hipMemcpyDeviceToHost));
     return fail(GK_E_ARG, "ids[%lld] = %d lies outside [0, %lld)", (long long)first, id, (long long)h->S);
   }
-  *nflush = h->h_ovf[GK_SEL_COUNT];
+  sel->nflush = h->h_ovf[GK_SEL_COUNT];
   return GK_OK;
-}
-
-// merge_compress() of the listed streams (each has n > 0 and pending values):
-// k_merge's explicit-record mode with no records, as gk_rollup flushes its
-// members; a stream that needs a larger class for it climbs run_merge's levels.
-static int select_flush(gk_set* h, const int32_t* list, int64_t nflush, hipStream_t s) {
-  if (nflush <= 0) return GK_OK;
-  MergeArgsHost a{};
-  a.src = h->st;
-  a.eoffs = h->d_zero_offs;
-  a.mode = 1;
-  a.list = list;
-  a.count = nflush;
-  return run_merge(h, a, s);
 }
 
 // End of a selection call that may have promoted streams: the counters (slots
@@ -1876,57 +1854,36 @@ static int select_end(gk_set* h, hipStream_t s) {
 }
 
 int gk_flush_select(gk_set* h, const int32_t* ids, int64_t count, void* stream) {
-  int rc = check_set(h);
-  if (!rc) rc = check_select_args(ids, count);
-  if (!rc) rc = gk_sync(h, stream);
-  if (rc || count == 0) return rc;
+  Selection sel;
+  int rc = select_begin(h, ids, count, true, stream, &sel);
+  if (rc || count == 0 || sel.nflush == 0) return rc;
   hipStream_t s = (hipStream_t)stream;
-  int32_t* list = nullptr;
-  int64_t nflush = 0;
-  rc = select_begin(h, ids, count, true, stream, &list, &nflush);
-  if (rc || nflush == 0) return rc;
-  rc = select_flush(h, list, nflush, s);
+  rc = flush_listed(h, sel.list, sel.nflush, s);
   return rc ? rc : select_end(h, s);
 }
 
 int gk_quantiles_select(gk_set* h, const int32_t* ids, int64_t count, const double* qs, int nq, double* out, int mode,
                         void* stream) {
-  int rc = check_set(h);
-  if (!rc) rc = check_select_args(ids, count);
-  if (rc) return rc;
-  // (the checks of prepare_query, ahead of anything else)
-  if (nq < 0 || (nq > 0 && (!qs || !out))) return fail(GK_E_ARG, "bad quantile arguments");
-  if (mode != GK_Q_LIST && mode != GK_Q_SINGLE) return fail(GK_E_ARG, "bad mode %d", mode);
-  for (int i = 0; i < nq; ++i)
-    if (std::isnan(qs[i])) return fail(GK_E_ARG, "cannot convert float NaN to integer");
-  rc = gk_sync(h, stream);
-  if (rc || count == 0) return rc;
+  Selection sel;
+  int rc = select_begin(h, ids, count, true, stream, &sel, [&] { return check_query_args(qs, nq, out, mode); });
+  if (rc || count == 0 || nq == 0) return rc;
   hipStream_t s = (hipStream_t)stream;
-  int32_t* list = nullptr;
-  int64_t nflush = 0;
-  rc = select_begin(h, ids, count, true, stream, &list, &nflush);
-  if (rc || nq == 0) return rc;
   GKQuery q;
   rc = prepare_query(h, qs, nq, out, mode, s, &q);  // (before the flush: its GK_E_NOMEM mutates nothing)
   if (rc) return rc;
   // gk:166-167 / gk:197-198: the listed streams with pending values are
   // flushed first (state mutation); then every row from its committed table
-  rc = select_flush(h, list, nflush, s);
+  rc = flush_listed(h, sel.list, sel.nflush, s);
   if (rc) return rc;  // (GK_E_OVERFLOW: out is not written)
   HIP_TRY(gk_launch_select_query(h->st, ids, count, q, s));
   return select_end(h, s);
 }
 
 int gk_reset_select(gk_set* h, const int32_t* ids, int64_t count, void* stream) {
-  int rc = check_set(h);
-  if (!rc) rc = check_select_args(ids, count);
-  if (!rc) rc = gk_sync(h, stream);
+  Selection sel;
+  int rc = select_begin(h, ids, count, false, stream, &sel);
   if (rc || count == 0) return rc;
   hipStream_t s = (hipStream_t)stream;
-  int32_t* list = nullptr;
-  int64_t nflush = 0;
-  rc = select_begin(h, ids, count, false, stream, &list, &nflush);
-  if (rc) return rc;
   // (class and slot stay: the stream's next ingest runs in its class's launch,
   // from an empty table)
   HIP_TRY(gk_launch_select_reset(h->st, ids, count, s));
@@ -1936,15 +1893,10 @@ int gk_reset_select(gk_set* h, const int32_t* ids, int64_t count, void* stream) 
 
 int gk_stats_select(gk_set* h, const int32_t* ids, int64_t count, int64_t* n, double* mn, double* mx, double* sum,
                     double* avg, int32_t* table_size, int32_t* pending, void* stream) {
-  int rc = check_set(h);
-  if (!rc) rc = check_select_args(ids, count);
-  if (!rc) rc = gk_sync(h, stream);
+  Selection sel;
+  int rc = select_begin(h, ids, count, false, stream, &sel);
   if (rc || count == 0) return rc;
   hipStream_t s = (hipStream_t)stream;
-  int32_t* list = nullptr;
-  int64_t nflush = 0;
-  rc = select_begin(h, ids, count, false, stream, &list, &nflush);
-  if (rc) return rc;
   const GKSelectStats o{n, mn, mx, sum, avg, table_size, pending};
   HIP_TRY(gk_launch_select_stats(h->st, ids, count, o, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -1952,13 +1904,6 @@ int gk_stats_select(gk_set* h, const int32_t* ids, int64_t count, int64_t* n, do
 }
 
 // ---- rank queries: bounds on each stream's count of values <= x (k_rank)
-
-static int check_rank_args(const double* xs, int nx, const int64_t* lo, const int64_t* hi) {
-  if (nx < 0 || (nx > 0 && (!xs || (!lo && !hi)))) return fail(GK_E_ARG, "bad rank arguments");
-  for (int i = 0; i < nx; ++i)
-    if (std::isnan(xs[i])) return fail(GK_E_ARG, "xs[%d] is NaN", i);
-  return GK_OK;
-}
 
 int gk_ranks(gk_set* h, const double* xs, int nx, int64_t* lo, int64_t* hi, void* stream) {
   int rc = check_set(h);
@@ -1980,19 +1925,13 @@ int gk_ranks(gk_set* h, const double* xs, int nx, int64_t* lo, int64_t* hi, void
 
 int gk_ranks_select(gk_set* h, const int32_t* ids, int64_t count, const double* xs, int nx, int64_t* lo, int64_t* hi,
                     void* stream) {
-  int rc = check_set(h);
-  if (!rc) rc = check_select_args(ids, count);
-  if (!rc) rc = check_rank_args(xs, nx, lo, hi);
-  if (!rc) rc = gk_sync(h, stream);
-  if (rc || count == 0) return rc;
+  Selection sel;
+  int rc = select_begin(h, ids, count, true, stream, &sel, [&] { return check_rank_args(xs, nx, lo, hi); });
+  if (rc || count == 0 || nx == 0) return rc;
   hipStream_t s = (hipStream_t)stream;
-  int32_t* list = nullptr;
-  int64_t nflush = 0;
-  rc = select_begin(h, ids, count, true, stream, &list, &nflush);
-  if (rc || nx == 0) return rc;
   rc = stage_qs(h, xs, nx, s);  // (before the flush, as in gk_quantiles_select)
   if (rc) return rc;
-  rc = select_flush(h, list, nflush, s);
+  rc = flush_listed(h, sel.list, sel.nflush, s);
   if (rc) return rc;  // (GK_E_OVERFLOW: lo and hi are not written)
   HIP_TRY(gk_launch_rank(h->st, ids, count, h->d_qs, nx, lo, hi, s));
   return select_end(h, s);
@@ -2001,16 +1940,8 @@ int gk_ranks_select(gk_set* h, const int32_t* ids, int64_t count, const double* 
 static int merge_self(gk_set* dst, hipStream_t s, void* stream);
 
 int gk_merge(gk_set* dst, gk_set* const* srcs, int nsrcs, void* stream) {
-  int rc = check_set(dst);
+  int rc = check_merge_args(dst, srcs, nsrcs);
   if (rc) return rc;
-  if (nsrcs < 0 || (nsrcs > 0 && !srcs)) return fail(GK_E_ARG, "bad source list");
-  for (int k = 0; k < nsrcs; ++k) {
-    if (!srcs[k]) return fail(GK_E_ARG, "null source %d", k);
-    if (srcs[k]->eps != dst->eps)  // gk:118-119
-      return fail(GK_E_EPS_MISMATCH, "Cannot merge two GKArrays with different epsilon values");
-    if (srcs[k]->S != dst->S)
-      return fail(GK_E_ARG, "stream counts differ (%lld vs %lld)", (long long)srcs[k]->S, (long long)dst->S);
-  }
   hipStream_t s = (hipStream_t)stream;
   rc = gk_sync(dst, stream);
   if (rc) return rc;
@@ -2023,12 +1954,7 @@ int gk_merge(gk_set* dst, gk_set* const* srcs, int nsrcs, void* stream) {
     }
     // a repeated source is flushed again at each of its merges (gk:137)
     rc = gk_sync(src, stream);
-    if (rc) return rc;
-    // other.merge_compress() -- unconditional in the reference (gk:126, 137)
-    rc = begin_call(src, s);
-    if (!rc) rc = run_ingest(src, nullptr, nullptr, 2, s);
-    if (!rc) rc = mark_done(src, s);
-    if (!rc) rc = gk_sync(src, stream);
+    if (!rc) rc = flush_source(src, s, stream);
     if (rc) return rc;
     MergeArgsHost a{};
     a.src = src->st;
@@ -2041,13 +1967,8 @@ int gk_merge(gk_set* dst, gk_set* const* srcs, int nsrcs, void* stream) {
 }
 
 int gk_rollup(gk_set* dst, gk_set* src, const int64_t* group_offsets, const int64_t* members, void* stream) {
-  int rc = check_set(dst);
-  if (!rc) rc = check_set(src);
+  int rc = check_rollup_args(dst, src, group_offsets);
   if (rc) return rc;
-  if (dst == src) return fail(GK_E_ARG, "roll-up of a set into itself");
-  if (!group_offsets) return fail(GK_E_ARG, "group_offsets is null");
-  if (src->eps != dst->eps)  // gk:118-119
-    return fail(GK_E_EPS_MISMATCH, "Cannot merge two GKArrays with different epsilon values");
   if (src->device != dst->device) return fail(GK_E_ARG, "the sets live on different devices");
   hipStream_t s = (hipStream_t)stream;
   rc = gk_sync(dst, stream);
@@ -2085,28 +2006,15 @@ int gk_rollup(gk_set* dst, gk_set* src, const int64_t* group_offsets, const int6
   if (M == S) {
     // every source stream is a member (the plain group-by): the batch flush
     // that gk_merge gives its sources; on a stream with n == 0 it changes nothing
-    rc = begin_call(src, s);
-    if (!rc) rc = run_ingest(src, nullptr, nullptr, 2, s);
-    if (!rc) rc = mark_done(src, s);
-    if (!rc) rc = gk_sync(src, stream);
-    if (rc) return rc;
+    rc = flush_source(src, s, stream);
   } else {
-    // k_merge's explicit-record mode with no records, over the list of those
-    // members; members that need a larger class for it climb run_merge's levels
+    // the list of those members; each climbs the ladder as far as its flush needs
     HIP_TRY(gk_launch_rollup_flush_list(src->st, members, M, word, scratch, s));
     const int64_t nflush = read_overflow(src, kRounds - 1, s);
     if (nflush < 0) return (int)nflush;
-    if (nflush > 0) {
-      MergeArgsHost a{};
-      a.src = src->st;
-      a.eoffs = src->d_zero_offs;
-      a.mode = 1;
-      a.list = scratch;
-      a.count = nflush;
-      rc = run_merge(src, a, s);
-      if (rc) return rc;
-    }
+    rc = flush_listed(src, scratch, nflush, s);
   }
+  if (rc) return rc;
   rc = run_rollup(dst, src, group_offsets, members, s);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(s));
@@ -2116,8 +2024,8 @@ int gk_rollup(gk_set* dst, gk_set* src, const int64_t* group_offsets, const int6
 int gk_merge_compress(gk_set* h, const double* v, const int32_t* g, const int32_t* d, const int64_t* eoffs,
                       void* stream) {
   int rc = check_set(h);
+  if (!rc) rc = check_record_args(v, g, d, eoffs);
   if (rc) return rc;
-  if (!eoffs || !v || !g || !d) return fail(GK_E_ARG, "null record arrays");
   hipStream_t s = (hipStream_t)stream;
   rc = gk_sync(h, stream);
   if (rc) return rc;
@@ -2410,10 +2318,7 @@ int gk_pack(gk_set* h, void* buf, int64_t bytes, void* stream) {
 // "other empty" branch whose flush of an empty stream changes nothing.
 static int merge_self(gk_set* dst, hipStream_t s, void* stream) {
   int rc = gk_sync(dst, stream);
-  if (!rc) rc = begin_call(dst, s);
-  if (!rc) rc = run_ingest(dst, nullptr, nullptr, 2, s);  // other.merge_compress() (gk:137)
-  if (!rc) rc = mark_done(dst, s);
-  if (!rc) rc = gk_sync(dst, stream);
+  if (!rc) rc = flush_source(dst, s, stream);  // other.merge_compress() (gk:137)
   if (rc) return rc;
   int64_t bytes = 0;
   rc = gk_pack_bytes(dst, &bytes, stream);

@@ -9,40 +9,11 @@
 // then the argument errors (nothing mutated, out_offsets all zero).
 // Built with ASan + UBSan by `make -C sketches-py_amd/cpu sanitize-keyed`;
 // tests/test_cpu_keyed.py runs it.
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
 #include <algorithm>
 #include <limits>
 #include <numeric>
-#include <random>
-#include <vector>
 
-#include "gk_cpu.h"
-
-extern "C" {
-typedef struct gko_set gko_set;
-gko_set* gko_create(int64_t S, double eps);
-void gko_destroy(gko_set* h);
-int gko_ingest(gko_set* h, const double* values, const int64_t* offs, int nthreads);
-void gko_stats(const gko_set* h, int64_t* n, double* mn, double* mx, double* sum, double* avg, int32_t* E,
-               int32_t* p);
-void gko_export(const gko_set* h, const int64_t* offs, double* v, int64_t* g, int64_t* d);
-void gko_export_pending(const gko_set* h, const int64_t* offs, double* v);
-}
-
-static int failures = 0;
-#define CHECK(c, ...)                   \
-  do {                                  \
-    if (!(c)) {                         \
-      fprintf(stderr, __VA_ARGS__);     \
-      fprintf(stderr, "\n");            \
-      ++failures;                       \
-      return;                           \
-    }                                   \
-  } while (0)
+#include "cpu_selftest_util.h"
 
 static double from_bits(uint64_t b) {
   double d;
@@ -115,43 +86,6 @@ static void group_cases() {
 }
 
 // ---- 2. keyed ingest vs the oracle's per-sample loop ------------------------
-struct State {
-  std::vector<int64_t> n, off, poff;
-  std::vector<double> f;
-  std::vector<int32_t> E, p, g, d;
-  std::vector<double> v, pv;
-};
-
-static State state_of(gk_set* a, int64_t S) {
-  State st;
-  st.n.resize(S);
-  st.f.resize(4 * S);
-  st.E.resize(S);
-  st.p.resize(S);
-  gk_stats(a, st.n.data(), st.f.data(), st.f.data() + S, st.f.data() + 2 * S, st.f.data() + 3 * S, st.E.data(),
-           st.p.data(), nullptr);
-  st.off.assign(S + 1, 0);
-  st.poff.assign(S + 1, 0);
-  for (int64_t s = 0; s < S; ++s) {
-    st.off[s + 1] = st.off[s] + st.E[s];
-    st.poff[s + 1] = st.poff[s] + st.p[s];
-  }
-  st.v.resize(st.off[S] + 1);
-  st.g.resize(st.off[S] + 1);
-  st.d.resize(st.off[S] + 1);
-  st.pv.resize(st.poff[S] + 1);
-  gk_export(a, st.off.data(), st.v.data(), st.g.data(), st.d.data(), nullptr);
-  gk_export_pending(a, st.poff.data(), st.pv.data(), nullptr);
-  return st;
-}
-
-static bool same_state(const State& a, const State& b) {
-  if (a.n != b.n || a.E != b.E || a.p != b.p || a.g != b.g || a.d != b.d) return false;
-  return memcmp(a.f.data(), b.f.data(), a.f.size() * 8) == 0 &&
-         memcmp(a.v.data(), b.v.data(), (a.v.size() - 1) * 8) == 0 &&
-         memcmp(a.pv.data(), b.pv.data(), (a.pv.size() - 1) * 8) == 0;
-}
-
 static void compare_with_oracle(gk_set* h, gko_set* o, int64_t S, const char* what) {
   const State st = state_of(h, S);
   std::vector<int64_t> n(S);
@@ -236,10 +170,5 @@ int main() {
   group_cases();
   ingest_case(0.1);
   ingest_case(0.01);
-  if (failures) {
-    fprintf(stderr, "cpu_keyed_selftest: %d failure(s)\n", failures);
-    return 1;
-  }
-  printf("cpu_keyed_selftest: ok\n");
-  return 0;
+  return selftest_result("cpu_keyed_selftest");
 }

@@ -7,153 +7,7 @@
 // values; a fresh and a pre-ingested destination; then the argument errors.
 // Built with ASan + UBSan by `make -C sketches-py_amd/cpu sanitize-rollup`;
 // tests/test_cpu_rollup.py runs it.
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <random>
-#include <vector>
-
-#include "gk_cpu.h"
-
-extern "C" {
-typedef struct gko_set gko_set;
-gko_set* gko_create(int64_t S, double eps);
-void gko_destroy(gko_set* h);
-int gko_ingest(gko_set* h, const double* values, const int64_t* offs, int nthreads);
-int gko_merge(gko_set* dst, gko_set* src, int nthreads);
-void gko_stats(const gko_set* h, int64_t* n, double* mn, double* mx, double* sum, double* avg, int32_t* E,
-               int32_t* p);
-void gko_export(const gko_set* h, const int64_t* offs, double* v, int64_t* g, int64_t* d);
-void gko_export_pending(const gko_set* h, const int64_t* offs, double* v);
-}
-
-static int failures = 0;
-#define CHECK(c, ...)                   \
-  do {                                  \
-    if (!(c)) {                         \
-      fprintf(stderr, __VA_ARGS__);     \
-      fprintf(stderr, "\n");            \
-      ++failures;                       \
-      return;                           \
-    }                                   \
-  } while (0)
-
-static bool same_bits(double a, double b) { return memcmp(&a, &b, 8) == 0; }
-
-// full state of a host-engine set
-struct State {
-  std::vector<int64_t> n, off, poff;
-  std::vector<double> f;  // mn, mx, sum, avg: 4 x S
-  std::vector<int32_t> E, p, g, d;
-  std::vector<double> v, pv;
-};
-
-static State state_of(gk_set* a, int64_t S) {
-  State st;
-  st.n.resize(S);
-  st.f.resize(4 * S);
-  st.E.resize(S);
-  st.p.resize(S);
-  gk_stats(a, st.n.data(), st.f.data(), st.f.data() + S, st.f.data() + 2 * S, st.f.data() + 3 * S, st.E.data(),
-           st.p.data(), nullptr);
-  st.off.assign(S + 1, 0);
-  st.poff.assign(S + 1, 0);
-  for (int64_t s = 0; s < S; ++s) {
-    st.off[s + 1] = st.off[s] + st.E[s];
-    st.poff[s + 1] = st.poff[s] + st.p[s];
-  }
-  st.v.resize(st.off[S] + 1);
-  st.g.resize(st.off[S] + 1);
-  st.d.resize(st.off[S] + 1);
-  st.pv.resize(st.poff[S] + 1);
-  gk_export(a, st.off.data(), st.v.data(), st.g.data(), st.d.data(), nullptr);
-  gk_export_pending(a, st.poff.data(), st.pv.data(), nullptr);
-  return st;
-}
-
-static bool same_state(const State& a, const State& b) {
-  if (a.n != b.n || a.E != b.E || a.p != b.p || a.g != b.g || a.d != b.d) return false;
-  return memcmp(a.f.data(), b.f.data(), a.f.size() * 8) == 0 && memcmp(a.v.data(), b.v.data(), (a.v.size() - 1) * 8) == 0 &&
-         memcmp(a.pv.data(), b.pv.data(), (a.pv.size() - 1) * 8) == 0;
-}
-
-// stream s of the engine's state against a one-stream oracle set
-static void compare_stream(const State& st, int64_t S, int64_t s, gko_set* o, const char* what) {
-  int64_t n = 0;
-  double f[4];
-  int32_t E = 0, p = 0;
-  gko_stats(o, &n, &f[0], &f[1], &f[2], &f[3], &E, &p);
-  CHECK(st.n[s] == n && st.E[s] == E && st.p[s] == p, "%s stream %lld: n %lld/%lld table %d/%d pending %d/%d", what,
-        (long long)s, (long long)st.n[s], (long long)n, st.E[s], E, st.p[s], p);
-  for (int k = 0; k < 4; ++k) CHECK(same_bits(st.f[k * S + s], f[k]), "%s stream %lld: stat %d", what, (long long)s, k);
-  const int64_t zero[2] = {0, 0};
-  std::vector<double> v(E + 1), pv(p + 1);
-  std::vector<int64_t> g(E + 1), d(E + 1);
-  gko_export(o, zero, v.data(), g.data(), d.data());
-  gko_export_pending(o, zero, pv.data());
-  for (int32_t k = 0; k < E; ++k)
-    CHECK(same_bits(st.v[st.off[s] + k], v[k]) && st.g[st.off[s] + k] == g[k] && st.d[st.off[s] + k] == d[k],
-          "%s stream %lld: record %d", what, (long long)s, k);
-  for (int32_t k = 0; k < p; ++k) CHECK(same_bits(st.pv[st.poff[s] + k], pv[k]), "%s stream %lld: pending %d", what,
-                                        (long long)s, k);
-}
-
-static std::vector<double> gen(std::mt19937_64& rng, int dist, int64_t L) {
-  std::vector<double> x(L);
-  std::uniform_real_distribution<double> u(0, 1);
-  std::lognormal_distribution<double> ln(0, 1);
-  std::uniform_int_distribution<int> small(0, 4);
-  for (int64_t i = 0; i < L; ++i) {
-    switch (dist) {
-      case 0: x[i] = u(rng); break;
-      case 1: x[i] = ln(rng); break;
-      case 2: x[i] = (double)(L - i); break;  // descending
-      case 3: x[i] = (double)i; break;        // ascending
-      case 4: x[i] = (double)small(rng); break;  // ties
-      default: x[i] = (small(rng) & 1) ? 0.0 : -0.0; break;  // signed zeros
-    }
-  }
-  return x;
-}
-
-struct Sets {
-  gk_set* eng = nullptr;
-  std::vector<gko_set*> orc;
-  int64_t S = 0;
-};
-
-static Sets make(double eps, const std::vector<int64_t>& lens, uint64_t seed) {
-  Sets z;
-  z.S = (int64_t)lens.size();
-  std::mt19937_64 rng(seed);
-  if (gk_create(z.S, eps, 0, -1, &z.eng) != GK_OK) {
-    ++failures;
-    return z;
-  }
-  gk_cpu_set_threads(z.eng, 4);
-  std::vector<double> flat;
-  std::vector<int64_t> offs(z.S + 1, 0);
-  for (int64_t s = 0; s < z.S; ++s) {
-    auto x = gen(rng, (int)(s % 6), lens[s]);
-    x.push_back(0);  // (never an empty buffer)
-    const int64_t one[2] = {0, lens[s]};
-    gko_set* o = gko_create(1, eps);
-    gko_ingest(o, x.data(), one, 1);
-    z.orc.push_back(o);
-    flat.insert(flat.end(), x.begin(), x.end() - 1);
-    offs[s + 1] = (int64_t)flat.size();
-  }
-  flat.push_back(0);
-  gk_ingest(z.eng, flat.data(), offs.data(), nullptr);
-  return z;
-}
-
-static void drop(Sets& z) {
-  gk_destroy(z.eng);
-  for (gko_set* o : z.orc) gko_destroy(o);
-}
+#include "cpu_selftest_util.h"
 
 static void run(bool pre) {
   const double eps = 0.01;
@@ -165,8 +19,8 @@ static void run(bool pre) {
   const int64_t G = (int64_t)groups.size();
   std::vector<int64_t> dlens = {1000, 57, 57, 0, 1000, 0, 57};
   if (!pre) dlens.assign(G, 0);
-  Sets src = make(eps, lens, 11), dst = make(eps, dlens, 12);
-  if (!src.eng || !dst.eng) return;
+  Sets src, dst;
+  if (!make(src, eps, lens, 11) || !make(dst, eps, dlens, 12)) return;
   std::vector<int64_t> go(G + 1, 0), mem;
   std::vector<char> is_member(src.S, 0);
   for (int64_t j = 0; j < G; ++j) {
@@ -212,10 +66,5 @@ static void run(bool pre) {
 int main() {
   run(false);
   run(true);
-  if (failures) {
-    fprintf(stderr, "cpu_rollup_selftest: %d failure(s)\n", failures);
-    return 1;
-  }
-  printf("cpu_rollup_selftest: ok\n");
-  return 0;
+  return selftest_result("cpu_rollup_selftest");
 }

@@ -4,42 +4,10 @@
 // requires identical state.  Built with ASan + UBSan by
 // `make -C sketches-py_amd/cpu sanitize` (sanitizers on the host
 // code); tests/test_cpu_sanitize.py runs it.
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
+#include "cpu_selftest_util.h"
 
-#include <random>
-#include <vector>
-
-#include "gk_cpu.h"
-
-extern "C" {
-typedef struct gko_set gko_set;
-gko_set* gko_create(int64_t S, double eps);
-void gko_destroy(gko_set* h);
-int gko_ingest(gko_set* h, const double* values, const int64_t* offs, int nthreads);
-int gko_flush(gko_set* h, int force, int nthreads);
-int gko_quantiles(gko_set* h, const double* qs, int nq, double* out, int mode, int nthreads);
-int gko_merge(gko_set* dst, gko_set* src, int nthreads);
-void gko_stats(const gko_set* h, int64_t* n, double* mn, double* mx, double* sum, double* avg, int32_t* E,
-               int32_t* p);
-void gko_export(const gko_set* h, const int64_t* offs, double* v, int64_t* g, int64_t* d);
-void gko_export_pending(const gko_set* h, const int64_t* offs, double* v);
-}
-
-static int failures = 0;
-#define CHECK(c, ...)                   \
-  do {                                  \
-    if (!(c)) {                         \
-      fprintf(stderr, __VA_ARGS__);     \
-      fprintf(stderr, "\n");            \
-      ++failures;                       \
-      return;                           \
-    }                                   \
-  } while (0)
-
-static bool same_bits(double a, double b) { return memcmp(&a, &b, 8) == 0 || (std::isnan(a) && std::isnan(b)); }
+// (quantile answers and stats: a NaN equals a NaN of any payload)
+static bool same_or_nan(double a, double b) { return same_bits(a, b) || (std::isnan(a) && std::isnan(b)); }
 
 static void compare(gk_set* a, gko_set* o, int64_t S, const char* what) {
   std::vector<int64_t> n1(S), n2(S);
@@ -50,7 +18,7 @@ static void compare(gk_set* a, gko_set* o, int64_t S, const char* what) {
   gko_stats(o, n2.data(), f2.data(), f2.data() + S, f2.data() + 2 * S, f2.data() + 3 * S, e2.data(), p2.data());
   for (int64_t s = 0; s < S; ++s) {
     CHECK(n1[s] == n2[s] && e1[s] == e2[s] && p1[s] == p2[s], "%s: stream %lld sizes", what, (long long)s);
-    for (int k = 0; k < 4; ++k) CHECK(same_bits(f1[k * S + s], f2[k * S + s]), "%s: stream %lld stat %d", what,
+    for (int k = 0; k < 4; ++k) CHECK(same_or_nan(f1[k * S + s], f2[k * S + s]), "%s: stream %lld stat %d", what,
                                       (long long)s, k);
   }
   std::vector<int64_t> off(S + 1, 0), poff(S + 1, 0);
@@ -67,26 +35,12 @@ static void compare(gk_set* a, gko_set* o, int64_t S, const char* what) {
   gk_export_pending(a, poff.data(), pv1.data(), nullptr);
   gko_export_pending(o, poff.data(), pv2.data());
   for (int64_t k = 0; k < E; ++k)
-    CHECK(same_bits(v1[k], v2[k]) && g1[k] == g2[k] && d1[k] == d2[k], "%s: record %lld", what, (long long)k);
-  for (int64_t k = 0; k < P; ++k) CHECK(same_bits(pv1[k], pv2[k]), "%s: pending %lld", what, (long long)k);
+    CHECK(same_or_nan(v1[k], v2[k]) && g1[k] == g2[k] && d1[k] == d2[k], "%s: record %lld", what, (long long)k);
+  for (int64_t k = 0; k < P; ++k) CHECK(same_or_nan(pv1[k], pv2[k]), "%s: pending %lld", what, (long long)k);
 }
 
-static std::vector<double> gen(std::mt19937_64& rng, int dist, int64_t L) {
-  std::vector<double> x(L);
-  std::uniform_real_distribution<double> u(0, 1);
-  std::lognormal_distribution<double> ln(0, 1);
-  std::uniform_int_distribution<int> small(0, 4);
-  for (int64_t i = 0; i < L; ++i) {
-    switch (dist) {
-      case 0: x[i] = u(rng); break;
-      case 1: x[i] = ln(rng); break;
-      case 2: x[i] = (double)(L - i); break;  // descending
-      case 3: x[i] = (double)small(rng); break;
-      default: x[i] = (small(rng) & 1) ? 0.0 : -0.0; break;
-    }
-  }
-  return x;
-}
+// the workload's distributions among gen()'s: uniform, lognormal, descending, ties, signed zeros
+static const int kDist[5] = {0, 1, 2, 4, 5};
 
 static void run(double eps, int64_t S, uint64_t seed) {
   std::mt19937_64 rng(seed);
@@ -107,10 +61,10 @@ static void run(double eps, int64_t S, uint64_t seed) {
     std::vector<double> fb;
     std::vector<int64_t> ob_offs(S + 1, 0);
     for (int64_t s = 0; s < S; ++s) {
-      auto x = gen(rng, (int)(rng() % 5), (int64_t)(rng() % (4 * P)));
+      auto x = gen(rng, kDist[rng() % 5], (int64_t)(rng() % (4 * P)));
       flat.insert(flat.end(), x.begin(), x.end());
       offs[s + 1] = (int64_t)flat.size();
-      auto y = gen(rng, (int)(rng() % 5), (int64_t)(rng() % (3 * P)));
+      auto y = gen(rng, kDist[rng() % 5], (int64_t)(rng() % (3 * P)));
       fb.insert(fb.end(), y.begin(), y.end());
       ob_offs[s + 1] = (int64_t)fb.size();
     }
@@ -128,7 +82,7 @@ static void run(double eps, int64_t S, uint64_t seed) {
     gko_flush(o, 1, 1);  // the oracle's caller flushes (gk:197-198)
     gko_quantiles(o, qs, 4, q2.data(), 0, 1);
     for (int64_t k = 0; k < 4 * S; ++k) {
-      if (!same_bits(q1[k], q2[k])) {
+      if (!same_or_nan(q1[k], q2[k])) {
         fprintf(stderr, "%s: quantile %lld\n", what, (long long)k);
         ++failures;
         break;
@@ -150,10 +104,5 @@ static void run(double eps, int64_t S, uint64_t seed) {
 int main() {
   const double eps[] = {0.2, 0.05, 0.01, 0.001};
   for (int k = 0; k < 4; ++k) run(eps[k], eps[k] >= 0.01 ? 300 : 40, 1000 + k);
-  if (failures) {
-    fprintf(stderr, "cpu_selftest: %d failure(s)\n", failures);
-    return 1;
-  }
-  printf("cpu_selftest: ok\n");
-  return 0;
+  return selftest_result("cpu_selftest");
 }

@@ -211,6 +211,47 @@ def case_narrow_ladder(dev):
     return tops
 
 
+def case_merge_ladder(dev):
+    """(GK_CAPS=128,256,512,4096 set by the caller) the other two folds of the
+    capacity-level ladder, each with a class-0 stream that climbs inside the
+    call beside one that stays below 128 entries: merge_from (stream 0, a
+    descending run of 190 values -- 51 entries and 89 pending values -- takes
+    150 lognormal values from the source) and merge_compress(entries) (stream
+    0 takes 300 records that its threshold of 1 keeps apart)."""
+    eps = 0.01
+    # (dist 3: a descending run, whose entries carry deltas that no later threshold removes)
+    sspecs, dspecs = [(1, 150, 831), (0, 57, 832), (0, 0, 833)], [(3, 190, 834), (2, 250, 835), (5, 101, 836)]
+    src, dst = make_set(dev, eps, sspecs), make_set(dev, eps, dspecs)
+    if dev != "cpu":
+        assert dst.capacity(1) == 256 and dst.capacity(2) == 512
+    src_o = [oracle_of(eps, sp) for sp in sspecs]
+    dst_o = [oracle_of(eps, sp) for sp in dspecs]
+    assert all(len(o.v) < 128 for o in dst_o)  # (every destination stream starts in class 0)
+    dst.merge_from([src])
+    for o, m in zip(dst_o, src_o):
+        o.merge(m)
+    assert len(dst_o[0].v) > 128 > len(dst_o[1].v) > 0, [len(o.v) for o in dst_o]
+    assert_set_matches(dst, dst_o, "merge ladder dst")
+    assert_set_matches(src, src_o, "merge ladder src")
+    # merge_compress(entries): n = 57 gives the threshold floor(2 eps (n - 1)) = 1, no two records combine
+    mspecs = [(1, 57, 837), (0, 57, 838), (5, 101, 836)]
+    mc, mc_o = make_set(dev, eps, mspecs), [oracle_of(eps, sp) for sp in mspecs]
+    recs = [[(0.5 + k, 1, 1) for k in range(300)], [(2.5, 1, 0), (7.0, 2, 1)], []]
+    flat = [r for rs in recs for r in rs]
+    offs = np.concatenate([[0], np.cumsum([len(rs) for rs in recs])])
+    mc.merge_compress(torch.tensor([r[0] for r in flat], dtype=torch.float64),
+                      torch.tensor([r[1] for r in flat], dtype=torch.int32),
+                      torch.tensor([r[2] for r in flat], dtype=torch.int32), torch.from_numpy(offs.astype(np.int64)))
+    for o, rs in zip(mc_o, recs):
+        o.flush(rs)
+    assert len(mc_o[0].v) > 128 > len(mc_o[1].v) > 0, [len(o.v) for o in mc_o]
+    assert_set_matches(mc, mc_o, "merge_compress ladder")
+    if dev != "cpu":
+        assert dst.num_promoted >= 1 and mc.num_promoted >= 1
+    assert_quantiles(dst, dst_o, "merge ladder dst")
+    assert_quantiles(mc, mc_o, "merge_compress ladder")
+
+
 def case_equivalence(dev):
     """keys = s % G: round r's members are the source slice [rG, (r+1)G); the
     same tables as one set per slice, folded by merge_from, give the same bits."""

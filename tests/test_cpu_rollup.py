@@ -21,6 +21,10 @@ def test_cpu_rollup_small_eps():
     C.case_small_eps("cpu")
 
 
+def test_cpu_merge_and_merge_compress_ladder_case():
+    C.case_merge_ladder("cpu")
+
+
 def test_cpu_rollup_equals_merge_from():
     C.case_equivalence("cpu")
 

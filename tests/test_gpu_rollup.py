@@ -29,6 +29,13 @@ def test_rollup_narrow_ladder_two_levels(gpu_device, monkeypatch):
     C.case_narrow_ladder(gpu_device)
 
 
+def test_merge_and_merge_compress_climb_narrow_ladder(gpu_device, monkeypatch):
+    """merge_from and merge_compress(entries) on the ladder 128,256,512,4096: a
+    class-0 stream climbs inside each call, beside one that stays in class 0."""
+    monkeypatch.setenv("GK_CAPS", "128,256,512,4096")
+    C.case_merge_ladder(gpu_device)
+
+
 def test_rollup_equals_merge_from(gpu_device):
     """Case 4: rollup_by_key(s % G) == merge_from of the source's slices."""
     C.case_equivalence(gpu_device)
