@@ -290,7 +290,11 @@ int gk_ranks_select(gk_set* set, const int32_t* ids, int64_t count,
  * itself (dst.merge(dst): dst is flushed, then merged with a snapshot of its
  * flushed state, as gk:137-154 do) and may repeat (flushed again at each of
  * its merges).  Returns GK_E_EPS_MISMATCH if any eps differs (gk:118-119) or
- * GK_E_ARG if the stream counts differ. */
+ * GK_E_ARG if the stream counts differ.  On GK_E_OVERFLOW (a merge outgrows
+ * the last capacity class or the count limit; the fold stops at that source)
+ * a stream that did not fit keeps its state from before that merge -- table,
+ * pending values, n, _min, _max, _sum, _avg -- the other streams are complete
+ * and the source has been flushed: gk_rollup's rule for a one-member group. */
 int gk_merge(gk_set* dst, gk_set* const* srcs, int nsrcs, void* stream);
 
 /* Group-by roll-up: GKArray.merge (gk:111-154) of groups of `src`'s streams
@@ -334,7 +338,9 @@ int gk_rollup(gk_set* dst, gk_set* src, const int64_t* group_offsets,
 /* GKArray.merge_compress(entries) with an explicit entry list (gk:63-109,
  * gk:71): stream s merges extra records [eoffs[s], eoffs[s+1]) given as
  * (v, g, d) device arrays, each list sorted by v as the reference requires of
- * its Entry lists. */
+ * its Entry lists.  On GK_E_OVERFLOW a stream that did not fit keeps its
+ * pre-call state (table, pending values, n, _min, _max, _sum, _avg) and the
+ * other streams are complete. */
 int gk_merge_compress(gk_set* set, const double* v, const int32_t* g,
                       const int32_t* d, const int64_t* eoffs, void* stream);
 

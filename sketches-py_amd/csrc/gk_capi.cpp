@@ -108,7 +108,7 @@ struct gk_set {
   bool void_defer = false;
   // the per-call counter block is known zero: gk_reset's k_reset zeroed it and
   // nothing has written it since (begin_call then skips its memset; cleared by
-  // begin_call and by the paths that write the block without it: run_merge,
+  // begin_call and by the paths that write the block without it: run_levels,
   // gk_import)
   bool ctr_clean = false;
   int32_t fatal_seen = 0;  // device FATAL count already reported
@@ -1133,74 +1133,50 @@ int run_levels(gk_set* dst, hipStream_t s, Launch&& launch, const char* overflow
   return fail(GK_E_OVERFLOW, overflow_fmt, (long long)todo, dst->st.cap[dst->st.nclass - 1]);
 }
 
-// The per-level fields of a fold's argument struct (MergeArgsHost / RollupArgsHost)
-template <typename Args>
-void set_level(Args& a, const GKState& dst, int cap, const int32_t* list, int64_t count, int32_t* ovf_count,
-               int32_t* ovf_list, unsigned char* ws, size_t ws_bytes, int64_t ws_blocks) {
-  a.dst = dst;
-  a.cap = cap;
-  a.list = list;
-  a.count = count;
-  a.ovf_count = ovf_count;
-  a.ovf_list = ovf_list;
-  a.ws = ws;
-  a.ws_bytes = ws_bytes;
-  a.ws_blocks = ws_blocks;
-}
+const char* const kMergeOverflow =
+    "%lld stream(s) exceed %d table entries in merge, or the per-stream count limit "
+    "2*eps*(n-1) <= 2^30";
+const char* const kRollupOverflow =
+    "%lld destination stream(s) exceed %d table entries in roll-up, or the per-stream count "
+    "limit 2*eps*(n-1) <= 2^30: they hold the fold of the members before the one that did not fit";
 
-// Merge / explicit merge_compress up the ladder.  base.list / base.count
-// (optional): only these streams at level 0 instead of every stream.
-int run_merge(gk_set* dst, const MergeArgsHost& base, hipStream_t s) {
-  MergeArgsHost a = base;
+// A fold (k_fold: merge, explicit merge_compress, roll-up) up the ladder; base
+// holds what stays the same at every level.  base.list / base.count
+// (optional): only these streams at level 0 instead of every stream.  A
+// destination whose fold stopped at a step that did not fit resumes at the
+// recorded step one level up.
+int run_fold(gk_set* dst, const FoldArgs& base, const char* overflow_fmt, hipStream_t s) {
+  FoldArgs a = base;
   return run_levels(
       dst, s,
       [&](int level, int cap, const int32_t* list, int64_t count, int32_t* ovf_count, int32_t* ovf_list,
           unsigned char* ws, size_t ws_bytes, int64_t ws_blocks) {
-        set_level(a, dst->st, cap, list, count, ovf_count, ovf_list, ws, ws_bytes, ws_blocks);
-        if (level == 0 && base.list) {
-          a.list = base.list;
-          a.count = base.count;
-        }
-        return gk_launch_merge(a, s);
-      },
-      "%lld stream(s) exceed %d table entries in merge, or the per-stream count limit "
-      "2*eps*(n-1) <= 2^30");
-}
-
-// The roll-up fold (k_rollup) up the ladder: a destination whose fold stopped
-// at a member that did not fit resumes at the recorded member one level up.
-int run_rollup(gk_set* dst, const gk_set* src, const int64_t* goffs, const int64_t* members, hipStream_t s) {
-  if (!dst->d_roll_prog && !renew_dev(&dst->d_roll_prog, (size_t)std::max<int64_t>(dst->S, 1) * sizeof(int64_t)))
-    return fail(GK_E_NOMEM, "roll-up progress array of %lld entries failed", (long long)dst->S);
-  RollupArgsHost a{};
-  a.src = src->st;
-  a.goffs = goffs;
-  a.members = members;
-  a.progress = dst->d_roll_prog;
-  return run_levels(
-      dst, s,
-      [&](int level, int cap, const int32_t* list, int64_t count, int32_t* ovf_count, int32_t* ovf_list,
-          unsigned char* ws, size_t ws_bytes, int64_t ws_blocks) {
-        set_level(a, dst->st, cap, list, count, ovf_count, ovf_list, ws, ws_bytes, ws_blocks);
+        const bool own = level == 0 && base.list;
+        a.dst = dst->st;
         a.resume = level > 0;
-        return gk_launch_rollup(a, s);
+        a.cap = cap;
+        a.list = own ? base.list : list;
+        a.count = own ? base.count : count;
+        a.ovf_count = ovf_count;
+        a.ovf_list = ovf_list;
+        a.ws = ws;
+        a.ws_bytes = ws_bytes;
+        a.ws_blocks = ws_blocks;
+        return gk_launch_fold(a, s);
       },
-      "%lld destination stream(s) exceed %d table entries in roll-up, or the per-stream count "
-      "limit 2*eps*(n-1) <= 2^30: they hold the fold of the members before the one that did not fit");
+      overflow_fmt);
 }
 
-// k_merge's explicit-record mode with no records over the n streams of `list`
+// k_fold's explicit-record step with no records over the n streams of `list`
 // (device): merge_compress() of each; a stream that needs a larger class for
 // it climbs the ladder.
 int flush_listed(gk_set* h, const int32_t* list, int64_t n, hipStream_t s) {
   if (n <= 0) return GK_OK;
-  MergeArgsHost a{};
-  a.src = h->st;
+  FoldArgs a{};
   a.eoffs = h->d_zero_offs;
-  a.mode = 1;
   a.list = list;
   a.count = n;
-  return run_merge(h, a, s);
+  return run_fold(h, a, kMergeOverflow, s);
 }
 
 // other.merge_compress() of every stream of a fold's source -- unconditional
@@ -1956,10 +1932,9 @@ int gk_merge(gk_set* dst, gk_set* const* srcs, int nsrcs, void* stream) {
     rc = gk_sync(src, stream);
     if (!rc) rc = flush_source(src, s, stream);
     if (rc) return rc;
-    MergeArgsHost a{};
+    FoldArgs a{};
     a.src = src->st;
-    a.mode = 0;
-    rc = run_merge(dst, a, s);
+    rc = run_fold(dst, a, kMergeOverflow, s);
     if (rc) return rc;
   }
   HIP_TRY(hipStreamSynchronize(s));
@@ -2015,7 +1990,14 @@ int gk_rollup(gk_set* dst, gk_set* src, const int64_t* group_offsets, const int6
     rc = flush_listed(src, scratch, nflush, s);
   }
   if (rc) return rc;
-  rc = run_rollup(dst, src, group_offsets, members, s);
+  if (!dst->d_roll_prog && !renew_dev(&dst->d_roll_prog, (size_t)std::max<int64_t>(dst->S, 1) * sizeof(int64_t)))
+    return fail(GK_E_NOMEM, "roll-up progress array of %lld entries failed", (long long)dst->S);
+  FoldArgs a{};
+  a.src = src->st;
+  a.goffs = group_offsets;
+  a.members = members;
+  a.progress = dst->d_roll_prog;
+  rc = run_fold(dst, a, kRollupOverflow, s);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(s));
   return GK_OK;
@@ -2029,14 +2011,12 @@ int gk_merge_compress(gk_set* h, const double* v, const int32_t* g, const int32_
   hipStream_t s = (hipStream_t)stream;
   rc = gk_sync(h, stream);
   if (rc) return rc;
-  MergeArgsHost a{};
-  a.src = h->st;
+  FoldArgs a{};
   a.ev = v;
   a.eg = g;
   a.ed = d;
   a.eoffs = eoffs;
-  a.mode = 1;
-  rc = run_merge(h, a, s);
+  rc = run_fold(h, a, kMergeOverflow, s);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(s));
   return GK_OK;
@@ -2309,12 +2289,12 @@ int gk_pack(gk_set* h, void* buf, int64_t bytes, void* stream) {
 
 // dst.merge(dst), gk:111-154 with `other` IS self: gk:137 flushes dst itself
 // (emptying its incoming), gk:138-147 convert that flushed table, gk:149
-// doubles n, and gk:154 merges the converted records back.  k_merge reads the
+// doubles n, and gk:154 merges the converted records back.  k_fold reads the
 // source table while it rewrites the destination's, so the source is a
 // snapshot of the flushed dst: packed into a device buffer and imported into
 // a scratch set that is NOT flushed again (a second compress at the same
 // threshold is not a no-op).  Its pending count is 0 and its n equals dst's,
-// so k_merge takes the general branch (n > 0) or, for an empty stream, the
+// so k_fold takes the general branch (n > 0) or, for an empty stream, the
 // "other empty" branch whose flush of an empty stream changes nothing.
 static int merge_self(gk_set* dst, hipStream_t s, void* stream) {
   int rc = gk_sync(dst, stream);
@@ -2334,10 +2314,9 @@ static int merge_self(gk_set* dst, hipStream_t s, void* stream) {
   if (!rc) rc = gkpack::import_packed<DevMem>(dst->self_scratch, buf.p, hd, stream);
   if (!rc) rc = gk_sync(dst->self_scratch, stream);
   if (rc) return (!err.empty()) ? fail(rc, "%s", err.c_str()) : rc;
-  MergeArgsHost a{};
+  FoldArgs a{};
   a.src = dst->self_scratch->st;
-  a.mode = 0;
-  rc = run_merge(dst, a, s);
+  rc = run_fold(dst, a, kMergeOverflow, s);
   // the snapshot set (a full copy of dst's state) is not kept beyond the
   // merge: the set's memory stays what it was before
   const int rs = gk_sync(dst, stream);

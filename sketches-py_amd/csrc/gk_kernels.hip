@@ -13,7 +13,8 @@
 //                           + optional fused quantiles (gk:156-232) answered
 //                           from the LDS table after the final flush: rank walk
 //                           as a count over the running max of prefix(g)+delta
-//   k_merge      gk:111-154 wave per stream: convert `other`, stable merge of
+//   k_fold       gk:111-154 wave per stream, per step (merge, roll-up member,
+//                           merge_compress(entries)): convert `other`, stable merge of
 //                           the incoming list, general four-rule walk (gk:76-106)
 //   k_select_*   gk:156-232, 45-46, 21-29  a list of stream ids: id check + flush
 //                           list, wave per row query, reset, stats gather
@@ -4793,32 +4794,15 @@ __global__ __launch_bounds__(64, W) void k_ingest_small(GKState st, const double
 }
 
 // ===========================================================================
-// k_merge: GKArray.merge (gk:111-154) and merge_compress(entries), stream by
-// stream.  The incoming list (self's raw pending values, then the converted
-// records of `other` or the caller's records) is stably ordered by value and
-// the four-rule walk of gk:76-106 runs wave-parallel over LDS: incoming
-// records carry g > 1 here, so the add-path closed form does not apply; each
-// lane re-walks its block of entries from its neighbour's carry until no
-// carry-in changes (k_merge).
+// The merge steps of k_fold: GKArray.merge (gk:111-154) and
+// merge_compress(entries), stream by stream.  The incoming list (self's raw
+// pending values, then the converted records of `other` or the caller's
+// records) is stably ordered by value and the four-rule walk of gk:76-106 runs
+// wave-parallel over LDS: incoming records carry g > 1 here, so the add-path
+// closed form does not apply; each lane re-walks its block of entries from its
+// neighbour's carry until no carry-in changes (k_fold).
 // `other` has already been flushed by the caller (gk:126, gk:137).
 // ===========================================================================
-struct MergeArgs {
-  GKState dst;
-  GKState src;            // mode 0: the other set (already flushed, gk:126/137)
-  const double* ev;       // mode 1: explicit records (v, g, d) in CSR
-  const int32_t* eg;
-  const int32_t* ed;
-  const int64_t* eoffs;
-  int mode;               // 0 = merge(other), 1 = merge_compress(entries)
-  int cap;                // LDS capacity for tables / records
-  const int32_t* list;    // streams to process (NULL = all)
-  int64_t count;
-  int32_t* ovf_count;
-  int32_t* ovf_list;
-  unsigned char* ws;      // global workspace (largest class), NULL = dynamic LDS
-  size_t ws_bytes;        // per block
-};
-
 struct MergeLDS {
   double *tv, *rv, *sp, *iv, *ov;
   int32_t *tg, *td, *rg, *rd, *ig, *id, *og, *od;
@@ -4854,7 +4838,7 @@ __device__ __forceinline__ void flag_overflow(int32_t* cnt, int32_t* list, int64
 
 #define GK_MERGE_RANK_MAX 256  // pending values ranked by comparison up to this many; bitonic above
 
-// The steps of one merge, shared by k_merge and k_rollup.  All of them work on
+// The steps of one merge.  All of them work on
 // the arrays of a MergeLDS carve (LDS or a block's global workspace).
 
 // gk:136-147: the converted records of a flushed `other` table into rv/rg/rd
@@ -5087,157 +5071,27 @@ __device__ __forceinline__ void merge_walk(const MergeLDS& m, int E, int M, int6
   }
 }
 
-template <bool GLOBAL>
-__global__ __launch_bounds__(64) void k_merge(MergeArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ int sh_out;
-  const int lane = threadIdx.x;
-  const int CAPL = a.cap;
-  const int PM = a.dst.pmax;
-  unsigned char* base = GLOBAL ? a.ws + (size_t)blockIdx.x * a.ws_bytes : smem;
-  const MergeLDS m = merge_carve(base, CAPL, PM);
-  const GKState& st = a.dst;
-  for (int64_t w = blockIdx.x; w < a.count; w += gridDim.x) {
-    const int64_t s = a.list ? (int64_t)a.list[w] : w;
-    GKRec* __restrict__ tab = gk_table_ptr(st, s);
-    const int outcap = min(st.cap[st.cls[s]], CAPL) - 1;  // k_ingest keeps one slot for padding
-    int64_t n = st.n[s];
-    const int E = st.E[s];
-    const int p = st.pend[s];
-    const double* __restrict__ pb = st.pbuf + s * (int64_t)st.pmax;
-
-    // ---- branch of gk:121-133 -------------------------------------------------
-    int nrec = 0;
-    if (a.mode == 0) {
-      const GKState& os = a.src;
-      const int64_t on = os.n[s];
-      const int oE = os.E[s];
-      const GKRec* __restrict__ otab = gk_table_ptr(os, s);
-      if (on != 0 && n == 0) {  // gk:125-133: take a copy of (flushed) other
-        if (oE > outcap) {
-          flag_overflow(a.ovf_count, a.ovf_list, s, lane);
-          __syncthreads();
-          continue;
-        }
-        for (int j = lane; j < oE; j += 64) tab[j] = otab[j];
-        if (lane == 0) {
-          st.n[s] = on;
-          st.E[s] = oE;
-          st.pend[s] = 0;
-          st.mn[s] = os.mn[s];
-          st.mx[s] = os.mx[s];
-          st.sum[s] = os.sum[s];
-          st.avg[s] = os.avg[s];
-        }
-        __syncthreads();
-        continue;
-      }
-      if (on != 0) {
-        // gk:136-147: spread from other's n, then the converted records
-        //   (other._min, g0+d0-spread-1), (v_k, g_{k+1}+d_{k+1}-d_k),
-        //   (v_{L-1}, spread+1-d_{L-1}); only g > 0 is kept.
-        const int64_t spread = (int64_t)(os.eps * (double)(on - 1));
-        const int ncand = oE + 1;
-        if (ncand > CAPL + 1) {
-          flag_overflow(a.ovf_count, a.ovf_list, s, lane);
-          __syncthreads();
-          continue;
-        }
-        nrec = merge_convert(m, otab, oE, spread, os.mn[s], lane);
-        n += on;  // gk:149
-        if (lane == 0) {  // gk:151-152: min()/max() keep self's value on ties
-          const double omn = os.mn[s], omx = os.mx[s];
-          if (omn < st.mn[s]) st.mn[s] = omn;
-          if (omx > st.mx[s]) st.mx[s] = omx;
-        }
-      }
-      // on == 0: gk:121-123, self.merge_compress() with no records
-    } else {
-      const int64_t eo = a.eoffs[s];
-      nrec = (int)(a.eoffs[s + 1] - eo);
-      if (nrec > CAPL + 1) {
-        flag_overflow(a.ovf_count, a.ovf_list, s, lane);
-        __syncthreads();
-        continue;
-      }
-      for (int c = lane; c < nrec; c += 64) {
-        m.rv[c] = a.ev[eo + c];
-        m.rg[c] = a.eg[eo + c];
-        m.rd[c] = a.ed[eo + c];
-      }
-    }
-    if (E > CAPL || !gk_count_ok(st, n)) {  // (n: after the merge, gk:149)
-      flag_overflow(a.ovf_count, a.ovf_list, s, lane);
-      __syncthreads();
-      continue;
-    }
-    merge_sort_pending(m, pb, p, lane);
-    merge_incoming(m, p, nrec, lane);
-    for (int j = lane; j < E; j += 64) {
-      const GKRec rc = tab[j];
-      m.tv[j] = rc.v;
-      m.tg[j] = rc.g;
-      m.td[j] = rc.d;
-    }
-    __syncthreads();
-    merge_walk(m, E, p + nrec, (int64_t)floor(st.two_eps * (double)(n - 1)) /* gk:70 */, outcap, lane, &sh_out);
-    __syncthreads();
-    const int no = sh_out;
-    if (no < 0) {
-      flag_overflow(a.ovf_count, a.ovf_list, s, lane);
-      __syncthreads();
-      continue;
-    }
-    for (int j = lane; j < no; j += 64) {
-      GKRec rc;
-      rc.v = m.ov[j];
-      rc.g = m.og[j];
-      rc.d = m.od[j];
-      tab[j] = rc;
-    }
-    if (lane == 0) {
-      st.n[s] = n;
-      st.E[s] = no;
-      st.pend[s] = 0;
-    }
-    __syncthreads();
-  }
-}
-
 // ===========================================================================
-// k_rollup: the group-by fold  dst[j].merge(src[members[k]])  for k in
-// [goffs[j], goffs[j+1])  (gk:111-154 per member), one wave per destination.
+// k_fold: dst[j].merge(step) over the steps of destination j (gk:111-154 per
+// step), one wave per destination.  gk_rollup, gk_merge and
+// gk_merge_compress(entries) all run it (FoldArgs, gk_launch.h): the steps are
+// the members src[members[k]], k in [goffs[j], goffs[j+1]), or without groups
+// the one member src[j], or with eoffs the caller's records (one step).
 // The destination's table is loaded into the carve once and stays there: each
 // member is converted (gk:136-147), merged with the destination's pending
-// values (first merge only, gk:71-72) and walked (gk:76-106) by k_merge's
-// steps, and the walk's output arrays become the table arrays of the next
-// member by a pointer swap.  Table and header go back to global memory once,
-// after the last member.  Members have been flushed by the caller (gk:126 /
-// gk:137; a member with n == 0 is not: gk:121-123).
-// A member whose merge does not fit this launch's capacity level ends the
-// fold there: the state after the member before it is committed (table, n,
-// _min, _max together, so nothing of the failed member is applied twice), its
-// position goes to progress[j] and j to the overflow list; the host raises
-// j's class and re-launches on the list with resume = 1.
+// values (first step only, gk:71-72) and walked (gk:76-106), and the walk's
+// output arrays become the table arrays of the next step by a pointer swap.
+// Table and header go back to global memory once, after the last step.
+// Members have been flushed by the caller (gk:126 / gk:137; a member with
+// n == 0 is not: gk:121-123).
+// A step that does not fit this launch's capacity level ends the fold there:
+// the state after the step before it is committed (table, n, _min, _max
+// together, so nothing of the failed step is applied twice; nothing at all
+// when no step fitted), its position goes to progress[j] and j to the overflow
+// list; the host raises j's class and re-launches on the list with resume = 1.
 // ===========================================================================
-struct RollupArgs {
-  GKState dst;
-  GKState src;
-  const int64_t* goffs;    // [G + 1]
-  const int64_t* members;  // [goffs[G]] streams of src, each at most once
-  int64_t* progress;       // [G] position of the first member not yet merged (listed destinations)
-  int resume;              // 0: start at goffs[j]; 1: at progress[j]
-  int cap;
-  const int32_t* list;     // destinations to process (NULL = all)
-  int64_t count;
-  int32_t* ovf_count;
-  int32_t* ovf_list;
-  unsigned char* ws;       // global workspace (classes beyond LDS), NULL = dynamic LDS
-  size_t ws_bytes;         // per block
-};
-
 template <bool GLOBAL>
-__global__ __launch_bounds__(64) void k_rollup(RollupArgs a) {
+__global__ __launch_bounds__(64) void k_fold(FoldArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ int sh_out;
   const int lane = threadIdx.x;
@@ -5246,11 +5100,17 @@ __global__ __launch_bounds__(64) void k_rollup(RollupArgs a) {
   const MergeLDS m0 = merge_carve(base, CAPL, a.dst.pmax);
   const GKState& st = a.dst;
   const GKState& os = a.src;
+  const bool recs = a.eoffs != nullptr;  // the step is the caller's records, not a member
   for (int64_t w = blockIdx.x; w < a.count; w += gridDim.x) {
     const int64_t j = a.list ? (int64_t)a.list[w] : w;
-    const int64_t kend = a.goffs[j + 1];
-    int64_t k = a.resume ? a.progress[j] : a.goffs[j];
+    // steps [k, kend): positions in members, or without groups the one member j
+    int64_t k = j, kend = j + 1;
+    if (a.goffs) {
+      kend = a.goffs[j + 1];
+      k = a.resume ? a.progress[j] : a.goffs[j];
+    }
     if (k >= kend) continue;  // an empty group: the destination is not touched (not flushed)
+    const int64_t k0 = k;
     GKRec* __restrict__ tab = gk_table_ptr(st, j);
     const int outcap = min(st.cap[st.cls[j]], CAPL) - 1;  // k_ingest keeps one slot for padding
     const double* __restrict__ pb = st.pbuf + j * (int64_t)st.pmax;
@@ -5258,73 +5118,92 @@ __global__ __launch_bounds__(64) void k_rollup(RollupArgs a) {
     int E = st.E[j];
     int p = st.pend[j];
     double mn = st.mn[j], mx = st.mx[j], sum = st.sum[j], avg = st.avg[j];
+    // the next member's id, n, table size and table address are loaded one
+    // member ahead (no merge of this fold writes src), off the chain of
+    // dependent steps -- the first one's beside the destination's header,
+    // ahead of the table load
+    int64_t ms_nx = 0, on_nx = 0;
+    int oE_nx = 0;
+    const GKRec* otab_nx = nullptr;
+    if (!recs) {
+      ms_nx = a.goffs ? a.members[k] : k;
+      on_nx = os.n[ms_nx];
+      oE_nx = os.E[ms_nx];
+      otab_nx = gk_table_ptr(os, ms_nx);
+    }
     MergeLDS m = m0;
-    if (E > CAPL) {  // the table itself needs a larger level: nothing done yet
-      if (lane == 0) a.progress[j] = k;
-      flag_overflow(a.ovf_count, a.ovf_list, j, lane);
+    bool ovf = E > CAPL;  // the table itself needs a larger level: nothing done yet
+    if (!ovf) {
+      for (int i = lane; i < E; i += 64) {
+        const GKRec rc = tab[i];
+        m.tv[i] = rc.v;
+        m.tg[i] = rc.g;
+        m.td[i] = rc.d;
+      }
       __syncthreads();
-      continue;
     }
-    for (int i = lane; i < E; i += 64) {
-      const GKRec rc = tab[i];
-      m.tv[i] = rc.v;
-      m.tg[i] = rc.g;
-      m.td[i] = rc.d;
-    }
-    __syncthreads();
-    bool ovf = false;
-    // the next member's id, n and table size are loaded one member ahead (no
-    // merge of this fold writes src), off the chain of dependent steps
-    int64_t ms_nx = a.members[k];
-    int64_t on_nx = os.n[ms_nx];
-    int oE_nx = os.E[ms_nx];
-    for (; k < kend; ++k) {
-      const int64_t ms = ms_nx;
-      const int64_t on = on_nx;
-      const int oE = oE_nx;
-      if (k + 1 < kend) {
-        ms_nx = a.members[k + 1];
-        on_nx = os.n[ms_nx];
-        oE_nx = os.E[ms_nx];
-      }
-      const GKRec* __restrict__ otab = gk_table_ptr(os, ms);
-      if (on != 0 && n == 0) {  // gk:125-133: take a copy of (flushed) other; E == p == 0 here
-        if (oE > outcap) {
-          ovf = true;
-          break;
-        }
-        for (int i = lane; i < oE; i += 64) {
-          const GKRec rc = otab[i];
-          m.tv[i] = rc.v;
-          m.tg[i] = rc.g;
-          m.td[i] = rc.d;
-        }
-        n = on;
-        E = oE;
-        p = 0;
-        mn = os.mn[ms];
-        mx = os.mx[ms];
-        sum = os.sum[ms];
-        avg = os.avg[ms];
-        __syncthreads();
-        continue;
-      }
+    for (; !ovf && k < kend; ++k) {
       int nrec = 0;
       int64_t n2 = n;
       double mn2 = mn, mx2 = mx;
-      if (on != 0) {
-        if (oE > CAPL) {  // (oE + 1 candidate records, rv holds CAPL + 1)
+      if (recs) {  // gk:63-109 with explicit entries
+        const int64_t eo = a.eoffs[j];
+        nrec = (int)(a.eoffs[j + 1] - eo);
+        if (nrec > CAPL + 1) {
           ovf = true;
           break;
         }
-        const int64_t spread = (int64_t)(os.eps * (double)(on - 1));  // gk:136
-        const double omn = os.mn[ms], omx = os.mx[ms];
-        nrec = merge_convert(m, otab, oE, spread, omn, lane);
-        n2 = n + on;  // gk:149
-        if (omn < mn2) mn2 = omn;  // gk:151-152: min()/max() keep self's value on ties
-        if (omx > mx2) mx2 = omx;
+        for (int c = lane; c < nrec; c += 64) {
+          m.rv[c] = a.ev[eo + c];
+          m.rg[c] = a.eg[eo + c];
+          m.rd[c] = a.ed[eo + c];
+        }
+      } else {
+        const int64_t ms = ms_nx;
+        const int64_t on = on_nx;
+        const int oE = oE_nx;
+        const GKRec* __restrict__ otab = otab_nx;
+        if (k + 1 < kend) {
+          ms_nx = a.members[k + 1];
+          on_nx = os.n[ms_nx];
+          oE_nx = os.E[ms_nx];
+          otab_nx = gk_table_ptr(os, ms_nx);
+        }
+        if (on != 0 && n == 0) {  // gk:125-133: take a copy of (flushed) other; E == p == 0 here
+          if (oE > outcap) {
+            ovf = true;
+            break;
+          }
+          for (int i = lane; i < oE; i += 64) {
+            const GKRec rc = otab[i];
+            m.tv[i] = rc.v;
+            m.tg[i] = rc.g;
+            m.td[i] = rc.d;
+          }
+          n = on;
+          E = oE;
+          p = 0;
+          mn = os.mn[ms];
+          mx = os.mx[ms];
+          sum = os.sum[ms];
+          avg = os.avg[ms];
+          __syncthreads();
+          continue;
+        }
+        if (on != 0) {
+          if (oE > CAPL) {  // (oE + 1 candidate records, rv holds CAPL + 1)
+            ovf = true;
+            break;
+          }
+          const int64_t spread = (int64_t)(os.eps * (double)(on - 1));  // gk:136
+          const double omn = os.mn[ms], omx = os.mx[ms];
+          nrec = merge_convert(m, otab, oE, spread, omn, lane);
+          n2 = n + on;  // gk:149
+          if (omn < mn2) mn2 = omn;  // gk:151-152: min()/max() keep self's value on ties
+          if (omx > mx2) mx2 = omx;
+        }
+        // on == 0: gk:121-123, self.merge_compress() with no records
       }
-      // on == 0: gk:121-123, self.merge_compress() with no records
       if (!gk_count_ok(st, n2)) {
         ovf = true;
         break;
@@ -5339,7 +5218,7 @@ __global__ __launch_bounds__(64) void k_rollup(RollupArgs a) {
         ovf = true;
         break;
       }
-      // the output is the next member's table
+      // the output is the next step's table
       { double* t = m.tv; m.tv = m.ov; m.ov = t; }
       { int32_t* t = m.tg; m.tg = m.og; m.og = t; }
       { int32_t* t = m.td; m.td = m.od; m.od = t; }
@@ -5349,25 +5228,29 @@ __global__ __launch_bounds__(64) void k_rollup(RollupArgs a) {
       mn = mn2;
       mx = mx2;
     }
-    // commit: the fold up to (not including) member k
-    for (int i = lane; i < E; i += 64) {
-      GKRec rc;
-      rc.v = m.tv[i];
-      rc.g = m.tg[i];
-      rc.d = m.td[i];
-      tab[i] = rc;
+    // commit: the fold up to (not including) step k
+    if (k != k0) {
+      for (int i = lane; i < E; i += 64) {
+        GKRec rc;
+        rc.v = m.tv[i];
+        rc.g = m.tg[i];
+        rc.d = m.td[i];
+        tab[i] = rc;
+      }
+      if (lane == 0) {
+        st.n[j] = n;
+        st.E[j] = E;
+        st.pend[j] = p;
+        st.mn[j] = mn;
+        st.mx[j] = mx;
+        st.sum[j] = sum;
+        st.avg[j] = avg;
+      }
     }
-    if (lane == 0) {
-      st.n[j] = n;
-      st.E[j] = E;
-      st.pend[j] = p;
-      st.mn[j] = mn;
-      st.mx[j] = mx;
-      st.sum[j] = sum;
-      st.avg[j] = avg;
-      if (ovf) a.progress[j] = k;
+    if (ovf) {
+      if (lane == 0 && a.progress) a.progress[j] = k;
+      flag_overflow(a.ovf_count, a.ovf_list, j, lane);
     }
-    if (ovf) flag_overflow(a.ovf_count, a.ovf_list, j, lane);
     __syncthreads();
   }
 }
@@ -6024,75 +5907,25 @@ size_t gk_merge_lds_bytes(int cap, int pmax) {
   return (b + 255) & ~(size_t)255;
 }
 
-hipError_t gk_launch_merge(const MergeArgsHost& h, hipStream_t stream) {
-  if (h.count <= 0) return hipSuccess;
-  MergeArgs a;
-  a.dst = h.dst;
-  a.src = h.src;
-  a.ev = h.ev;
-  a.eg = h.eg;
-  a.ed = h.ed;
-  a.eoffs = h.eoffs;
-  a.mode = h.mode;
-  a.cap = h.cap;
-  a.list = h.list;
-  a.count = h.count;
-  a.ovf_count = h.ovf_count;
-  a.ovf_list = h.ovf_list;
-  a.ws = h.ws;
-  a.ws_bytes = h.ws_bytes;
-  const size_t lds = gk_merge_lds_bytes(h.cap, h.dst.pmax);
-  if (h.ws) {
-    if (h.ws_bytes < lds || h.ws_blocks <= 0) return hipErrorInvalidValue;
-    int64_t grid = h.ws_blocks;
-    if (grid > h.count) grid = h.count;
-    hipLaunchKernelGGL(k_merge<true>, dim3((unsigned)grid), dim3(64), 0, stream, a);
+hipError_t gk_launch_fold(const FoldArgs& a, hipStream_t stream) {
+  if (a.count <= 0) return hipSuccess;
+  if (a.goffs && a.eoffs) return hipErrorInvalidValue;  // explicit records are one step
+  const size_t lds = gk_merge_lds_bytes(a.cap, a.dst.pmax);
+  if (a.ws) {
+    if (a.ws_bytes < lds || a.ws_blocks <= 0) return hipErrorInvalidValue;
+    const int64_t grid = std::min(a.ws_blocks, a.count);
+    hipLaunchKernelGGL(k_fold<true>, dim3((unsigned)grid), dim3(64), 0, stream, a);
     return hipGetLastError();
   }
   if (lds > 160 * 1024 - 64) return hipErrorInvalidValue;
   if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)k_merge<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  int64_t grid = (int64_t)num_cu() * 8;
-  if (grid > h.count) grid = h.count;
-  hipLaunchKernelGGL(k_merge<false>, dim3((unsigned)grid), dim3(64), lds, stream, a);
-  return hipGetLastError();
-}
-
-hipError_t gk_launch_rollup(const RollupArgsHost& h, hipStream_t stream) {
-  if (h.count <= 0) return hipSuccess;
-  RollupArgs a;
-  a.dst = h.dst;
-  a.src = h.src;
-  a.goffs = h.goffs;
-  a.members = h.members;
-  a.progress = h.progress;
-  a.resume = h.resume;
-  a.cap = h.cap;
-  a.list = h.list;
-  a.count = h.count;
-  a.ovf_count = h.ovf_count;
-  a.ovf_list = h.ovf_list;
-  a.ws = h.ws;
-  a.ws_bytes = h.ws_bytes;
-  // (k_merge's carve: the fold swaps its table and output arrays, no array more)
-  const size_t lds = gk_merge_lds_bytes(h.cap, h.dst.pmax);
-  if (h.ws) {
-    if (h.ws_bytes < lds || h.ws_blocks <= 0) return hipErrorInvalidValue;
-    int64_t grid = h.ws_blocks;
-    if (grid > h.count) grid = h.count;
-    hipLaunchKernelGGL(k_rollup<true>, dim3((unsigned)grid), dim3(64), 0, stream, a);
-    return hipGetLastError();
-  }
-  if (lds > 160 * 1024 - 64) return hipErrorInvalidValue;
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)k_rollup<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  // one block per destination (up to 2^20; the kernel's loop takes the rest):
-  // a fold is a long chain of dependent steps, so every wave the LDS carve
-  // lets a CU hold should be resident, and folds of uneven length are handed
-  // out as blocks retire
-  int64_t grid = (int64_t)1 << 20;
-  if (grid > h.count) grid = h.count;
-  hipLaunchKernelGGL(k_rollup<false>, dim3((unsigned)grid), dim3(64), lds, stream, a);
+    (void)hipFuncSetAttribute((const void*)k_fold<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  // groups: one block per destination (up to 2^20; the kernel's loop takes the
+  // rest) -- a fold is a long chain of dependent steps, so every wave the LDS
+  // carve lets a CU hold should be resident, and folds of uneven length are
+  // handed out as blocks retire.  One step each: 8 blocks per CU over the loop.
+  const int64_t grid = std::min(a.goffs ? (int64_t)1 << 20 : (int64_t)num_cu() * 8, a.count);
+  hipLaunchKernelGGL(k_fold<false>, dim3((unsigned)grid), dim3(64), lds, stream, a);
   return hipGetLastError();
 }
 

@@ -20,24 +20,6 @@ struct GKQuery {
   int mode = 0;                // 0 quantiles() list semantics, 1 quantile() per q
 };
 
-struct MergeArgsHost {
-  GKState dst;
-  GKState src;
-  const double* ev;
-  const int32_t* eg;
-  const int32_t* ed;
-  const int64_t* eoffs;
-  int mode;  // 0 = merge(other), 1 = merge_compress(entries)
-  int cap;
-  const int32_t* list;
-  int64_t count;
-  int32_t* ovf_count;
-  int32_t* ovf_list;
-  unsigned char* ws;  // global workspace for capacities beyond LDS (NULL = LDS)
-  size_t ws_bytes;    // per block
-  int64_t ws_blocks;
-};
-
 int gk_num_cu();
 // the device has CUs to spare for k_long_prep beside an early k_ingest_wg grid
 int gk_wg_early_ok();
@@ -157,30 +139,39 @@ hipError_t gk_launch_hc_fallback(const GKState& st, const double* x, const int64
 hipError_t gk_launch_query_list(const GKState& st, const int32_t* list, const int32_t* count, const GKQuery& q,
                                 bool qfix, hipStream_t stream);
 size_t gk_merge_lds_bytes(int cap, int pmax);
-hipError_t gk_launch_merge(const MergeArgsHost& h, hipStream_t stream);
-// k_rollup: the fold dst[j].merge(src[members[k]]), k in [goffs[j], goffs[j+1]),
-// one wave per destination with its table on chip across the members.  cap /
-// list / count / ovf_* / ws* as MergeArgsHost (the workspace is k_merge's).  A
-// destination that outgrows `cap` commits the fold before the member that did
-// not fit, records that member's position in progress[j] and joins the
-// overflow list; resume = 1 starts each listed destination at progress[j].
-struct RollupArgsHost {
+// k_fold: dst[j].merge(...) over the steps of destination j, one wave per
+// destination with its table on chip across the steps (gk:111-154 per step).
+// The host fills this struct and the kernel takes it as it is.
+//  * goffs given (roll-up): the steps are src[members[k]], k in [goffs[j],
+//    goffs[j+1]); an empty group leaves j untouched.  One block per destination.
+//  * goffs NULL: the one step src[j] (gk_merge), or with eoffs given the
+//    caller's records ev/eg/ed[eoffs[j] .. eoffs[j+1]) (merge_compress(entries),
+//    gk:63-109; src is not read).  num_cu * 8 blocks; progress may be NULL.
+// A step that does not fit `cap` ends the fold there: the state after the step
+// before it is committed (nothing when it was the first), its position goes to
+// progress[j] and j to the overflow list; resume = 1 starts each listed
+// destination at progress[j].
+struct FoldArgs {
   GKState dst;
   GKState src;             // its members already flushed (gk:126 / gk:137)
-  const int64_t* goffs;    // device [G + 1]
-  const int64_t* members;  // device [goffs[G]]
-  int64_t* progress;       // device [G]
-  int resume;
-  int cap;
-  const int32_t* list;
+  const int64_t* goffs;    // device [G + 1], or NULL
+  const int64_t* members;  // device [goffs[G]] streams of src, each at most once
+  int64_t* progress;       // device [G] position of the first step not yet merged (listed destinations)
+  int resume;              // 0: start at goffs[j]; 1: at progress[j]
+  const double* ev;        // explicit records (v, g, d) in CSR by eoffs (NULL: none)
+  const int32_t* eg;
+  const int32_t* ed;
+  const int64_t* eoffs;
+  int cap;                 // capacity of the carve for tables / records
+  const int32_t* list;     // destinations to process (NULL = all)
   int64_t count;
   int32_t* ovf_count;
   int32_t* ovf_list;
-  unsigned char* ws;
-  size_t ws_bytes;
+  unsigned char* ws;  // global workspace for capacities beyond LDS (NULL = LDS)
+  size_t ws_bytes;    // per block
   int64_t ws_blocks;
 };
-hipError_t gk_launch_rollup(const RollupArgsHost& h, hipStream_t stream);
+hipError_t gk_launch_fold(const FoldArgs& a, hipStream_t stream);
 // roll-up argument checks into *bad (zeroed by the caller): bit 0 offsets not
 // starting at 0 or decreasing, bit 1 a member outside [0, S), bit 2 a source
 // stream listed twice (bitmap: (S + 31) / 32 zeroed words)

@@ -252,6 +252,64 @@ def case_merge_ladder(dev):
     assert_quantiles(mc, mc_o, "merge_compress ladder")
 
 
+def case_merge_overflow(dev):
+    """(GK_CAPS=128,200 set by the caller: the last class holds 199 entries)
+    GK_E_OVERFLOW of merge_from and of merge_compress(entries): the stream that
+    did not fit keeps its state from before the call -- table, pending values,
+    n, min, max, sum, avg -- the other stream is complete, the source flushed.
+    Stream 0 of merge_from: 51 entries and 89 pending values take a source that
+    flushes to 138 entries (it fits); the merge would have 221.  The source's
+    min lies below the destination's and its max above, so a header written
+    before the overflow is known would show."""
+    from gkarray_amd._lib import GK_E_OVERFLOW, GKBackendError
+    eps = 0.01
+    sspecs, dspecs = [(3, 190, 840), (0, 57, 832)], [(3, 190, 834), (2, 250, 835)]
+    src, dst = make_set(dev, eps, sspecs), make_set(dev, eps, dspecs)
+    assert dst.capacity(1) == 200 and dst.capacity(2) == -1
+    limit = dst.capacity(1) - 1  # (one slot of a class is padding)
+    src_o = [oracle_of(eps, sp) for sp in sspecs]
+    dst_o = [oracle_of(eps, sp) for sp in dspecs]
+    assert [(len(o.v), len(o.pending)) for o in dst_o] == [(51, 89), (94, 48)]
+    assert src_o[0].min < dst_o[0].min and src_o[0].max > dst_o[0].max
+    merged = copy.deepcopy((dst_o, src_o))
+    for o, m in zip(*merged):
+        o.merge(m)  # (flushes m, gk:126 / gk:137)
+    assert [len(o.v) for o in merged[1]] == [138, 57] and [len(o.v) for o in merged[0]] == [221, 123]
+    assert 138 <= limit < 221
+    before = snapshot(dst)
+    with pytest.raises(GKBackendError) as ei:
+        dst.merge_from([src])
+    assert ei.value.code == GK_E_OVERFLOW, ei.value
+    after = snapshot(dst)
+    assert_stream(stream_of_snapshot(after, 0), stream_of_snapshot(before, 0),
+                  "merge_from overflow: dst 0 vs its state before the call")
+    assert_stream(stream_of_snapshot(after, 0), stream_of_oracle(dst_o[0]), "merge_from overflow: dst 0")
+    assert_stream(stream_of_snapshot(after, 1), stream_of_oracle(merged[0][1]), "merge_from overflow: dst 1")
+    assert_set_matches(src, merged[1], "merge_from overflow: src")
+    # merge_compress(entries): 150 records fit the carve (at most cap + 1), so
+    # it is the walk's output of 207 entries that does not fit
+    mspecs = [(1, 57, 837), (0, 57, 838)]
+    mc, mc_o = make_set(dev, eps, mspecs), [oracle_of(eps, sp) for sp in mspecs]
+    recs = [[(0.5 + k, 1, 1) for k in range(150)], [(2.5, 1, 0), (7.0, 2, 1)]]
+    flat = [r for rs in recs for r in rs]
+    offs = np.concatenate([[0], np.cumsum([len(rs) for rs in recs])])
+    flushed = copy.deepcopy(mc_o)
+    for o, rs in zip(flushed, recs):
+        o.flush(rs)
+    assert len(flushed[0].v) == 207 > limit and len(recs[0]) <= limit + 2, len(flushed[0].v)
+    before = snapshot(mc)
+    with pytest.raises(GKBackendError) as ei:
+        mc.merge_compress(torch.tensor([r[0] for r in flat], dtype=torch.float64),
+                          torch.tensor([r[1] for r in flat], dtype=torch.int32),
+                          torch.tensor([r[2] for r in flat], dtype=torch.int32), torch.from_numpy(offs.astype(np.int64)))
+    assert ei.value.code == GK_E_OVERFLOW, ei.value
+    after = snapshot(mc)
+    assert_stream(stream_of_snapshot(after, 0), stream_of_snapshot(before, 0),
+                  "merge_compress overflow: stream 0 vs its state before the call")
+    assert_stream(stream_of_snapshot(after, 0), stream_of_oracle(mc_o[0]), "merge_compress overflow: stream 0")
+    assert_stream(stream_of_snapshot(after, 1), stream_of_oracle(flushed[1]), "merge_compress overflow: stream 1")
+
+
 def case_equivalence(dev):
     """keys = s % G: round r's members are the source slice [rG, (r+1)G); the
     same tables as one set per slice, folded by merge_from, give the same bits."""

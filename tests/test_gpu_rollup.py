@@ -1,4 +1,4 @@
-"""Group-by roll-up on the MI355X engine (k_rollup through gk_rollup /
+"""Group-by roll-up on the MI355X engine (k_fold through gk_rollup /
 StreamSet.rollup_from / rollup_by_key): every case of tests/rollup_cases.py,
 bit for bit against the oracle's loop of GKArray.merge (gk:111-154)."""
 import pytest
@@ -34,6 +34,14 @@ def test_merge_and_merge_compress_climb_narrow_ladder(gpu_device, monkeypatch):
     class-0 stream climbs inside each call, beside one that stays in class 0."""
     monkeypatch.setenv("GK_CAPS", "128,256,512,4096")
     C.case_merge_ladder(gpu_device)
+
+
+def test_merge_and_merge_compress_overflow_keep_state(gpu_device, monkeypatch):
+    """GK_E_OVERFLOW of merge_from and merge_compress(entries) on the ladder
+    128,200: the stream that did not fit is bit-identical to before the call
+    (min / max included), the other stream complete, the source flushed."""
+    monkeypatch.setenv("GK_CAPS", "128,200")
+    C.case_merge_overflow(gpu_device)
 
 
 def test_rollup_equals_merge_from(gpu_device):

@@ -9,7 +9,7 @@ that state, re-ingested (reset + ingest) before every timed call:
   Q:  quantiles(qs) of the whole set, 3 quantiles (one k_ingest_small launch
       that flushes and answers every stream).
   RS: ranks_select(ids, xs) of --ids random streams (k_select_check, the flush
-      of the listed streams through k_merge, k_rank).
+      of the listed streams through k_fold, k_rank).
   QS: quantiles_select(ids, qs) of the same streams (the same check and flush,
       k_select_query).
 Each pair reads the same tables after the same flush.  One warm-up of each,

@@ -2,11 +2,11 @@
 
 Source: the cfg3 data (10^6 streams x 1000 Pareto values, eps 0.01), rolled up
 with keys = s % 10^4 into 10^4 destination streams.
-  A: dst.rollup_by_key(src, keys) into a fresh set (k_rollup: one launch per
+  A: dst.rollup_by_key(src, keys) into a fresh set (k_fold with groups: one launch per
      capacity level, the destination table on chip across its 100 members).
   B: the way without gk_rollup: the same tables held as 100 sets of 10^4
      streams (contiguous slices, import_arrays), then dst.merge_from(sets)
-     (100 k_merge folds, every destination table through HBM each time).
+     (100 one-step k_fold launches, every destination table through HBM each time).
 The source state is restored before every run (merges flush their sources).
 One warm-up run of each side, then --reps interleaved repetitions, wall time
 around the synchronising calls; medians are printed as one JSON line.  A's and

@@ -4,7 +4,7 @@ State: --streams streams x --values lognormal values, eps 0.01 (150 values:
 every stream holds 49 pending values).  From that state, re-ingested (reset +
 ingest) before every timed call:
   A: quantiles_select(ids, qs) of --ids random streams (k_select_check, the
-     flush of the listed streams through k_merge, k_select_query).
+     flush of the listed streams through k_fold, k_select_query).
   B: quantiles(qs) of the whole set (one k_ingest_small launch that flushes and
      answers every stream).
   A2: A again on the state A left (nothing pending in the listed streams: the
