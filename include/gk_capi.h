@@ -36,8 +36,9 @@
  *    and re-run from them by the host runtime before the next call proceeds.
  *    gk_merge, gk_rollup, gk_quantiles_select, gk_flush_select,
  *    gk_reset_select, gk_stats_select, gk_ranks, gk_ranks_select,
- *    gk_merge_compress, gk_import, gk_save / gk_load and gk_num_promoted
- *    synchronise before returning.
+ *    gk_merge_compress, gk_import, gk_save / gk_load, gk_pack_select_bytes,
+ *    gk_pack_select, gk_unpack_select and gk_num_promoted synchronise before
+ *    returning.
  *  - Limits.  Any finite eps > 0 with int(1/eps)+1 < 2^24 is accepted (the
  *    reference: any eps; eps > 1 gives a flush period of 1, gk:60); tables grow through capacity classes up to 2^27 entries per
  *    stream (the last classes are allocated on first use).  One stream may
@@ -405,6 +406,72 @@ int gk_pack(gk_set* set, void* buf, int64_t bytes, void* stream);
  * headers and offset tables are checked for consistency, but the buffers'
  * own lengths are not known to this call. */
 int gk_fold_packed(gk_set* dst, const void* const* bufs, int nbufs, void* stream);
+
+/* ---- stream transfer: a LIST of streams to and from a packed state ----------
+ * What the reference's user does with a dict of GKArray objects -- pickle
+ * sketches[k] and hand it to another process, delete cold keys, add new ones
+ * -- for the streams ids[0 .. count) of a set.  The carrier is the packed state
+ * above (GKPACK01 version 1, sketches-py_amd/csrc/gk_pack.h), identical for
+ * both engines.  Neither call flushes: after gk_pack_select -> any byte
+ * transport -> gk_unpack_select the destination stream answers every later
+ * call (ingest, flush, quantiles, ranks, merge, roll-up) with the bits the
+ * source stream would have given, across sets, devices and the two engines.
+ *  - Memory.  `ids` (int32) and `buf` are device memory for the GPU engine,
+ *    host memory for the CPU engine.
+ *  - Count and ids as gk_quantiles_select checks them: 0 <= count <= 2^31-1;
+ *    an id outside [0, S), negative ids included, is GK_E_ARG, returned BEFORE
+ *    anything is mutated or written, with the first bad index and its id in
+ *    the message.
+ *  - Synchronisation.  All three calls settle the set's earlier asynchronous
+ *    work and errors first (gk_sync: deferred streams are re-run, a sticky
+ *    error is returned instead of doing the work) and synchronise before
+ *    returning.
+ *
+ * gk_pack_select_bytes: the size gk_pack_select needs for these ids.
+ * gk_pack_select: writes a packed state whose header has S == count and whose
+ *   stream k is the complete state of stream ids[k] -- table, pending values
+ *   in insertion order, n/_min/_max/_sum/_avg -- exactly what gk_pack would
+ *   write for a set made of those streams; gk_fold_packed of this one buffer
+ *   into a set of `count` streams with the same eps therefore gives a set
+ *   holding the listed streams.
+ *    - No flush, no mutation: the set is bit-identical after the call (GPU
+ *      engine: capacity class and slot too).
+ *    - Ids may repeat and come in any order; row k always belongs to ids[k].
+ *    - count == 0 is valid (`ids` may be NULL): a packed state of zero streams.
+ *    - `bytes` below the needed size is GK_E_ARG with the needed size in the
+ *      message; nothing beyond `bytes` is written and the buffer's contents
+ *      are then unspecified.  Bytes past the packed size stay untouched, as
+ *      with gk_pack.
+ * gk_unpack_select: replaces the complete state of stream ids[k] with the
+ *   buffer's stream k.  Refused BEFORE anything is mutated:
+ *    - GK_E_ARG: an id outside [0, S); an id listed more than once (two rows
+ *      for one stream); the header's S != count; a stream whose pending count
+ *      p is not one add() can leave (p > n mod P, or n < 0: gk_import's rule);
+ *    - GK_E_EPS_MISMATCH: the buffer's eps differs from the set's;
+ *    - GK_E_FORMAT: bad magic, version or header size; inconsistent totals or
+ *      byte count; offsets not monotone from 0 to the header's totals;
+ *    - GK_E_OVERFLOW (GPU engine): a table with more entries than the last
+ *      capacity class holds (a GK_CAPS ladder shorter than the packing set's).
+ *   Table contents (order of v, values of g and delta) are not checked, as
+ *   gk_import does not check them; the buffer's own length is not known, as
+ *   for gk_fold_packed.  count == 0: the buffer is still validated (its S
+ *   must be 0) and nothing is touched.
+ *    - Unlisted streams stay bit-identical, including class and slot.
+ *    - Capacity class (GPU engine).  A listed stream whose new table fits its
+ *      class keeps class and slot; it is never demoted (gk_reset_select's
+ *      reasons); one whose table does not fit moves up to the first class
+ *      that holds it, and gk_num_promoted may rise.
+ *    - GK_E_NOMEM while growing a class arena is returned before the first
+ *      write: every listed stream then holds its complete old state.  At any
+ *      point a stream holds either its complete old or its complete new
+ *      state, never header words of one and the table of the other.
+ *  - Scratch (GPU engine; the selection scratch, owned by the set, only grows,
+ *    freed by gk_destroy).  gk_pack_select*: 32 bytes + 8 bytes per 2048
+ *    listed ids (the scan's tile sums).  gk_unpack_select: 32 bytes + S/8
+ *    bytes + 4 bytes per listed id (at most 4 S). */
+int gk_pack_select_bytes(gk_set* set, const int32_t* ids, int64_t count, int64_t* bytes, void* stream);
+int gk_pack_select(gk_set* set, const int32_t* ids, int64_t count, void* buf, int64_t bytes, void* stream);
+int gk_unpack_select(gk_set* set, const int32_t* ids, int64_t count, const void* buf, void* stream);
 
 /* Introspection for tests and benchmarks. */
 int64_t gk_num_streams(const gk_set* set);

@@ -984,6 +984,134 @@ int gk_fold_packed(gk_set* dst, const void* const* bufs, int nbufs, void* stream
   return (rc && !err.empty()) ? fail(rc, "%s", err.c_str()) : rc;
 }
 
+// ---- stream transfer: listed streams to and from a packed state (gk_capi.h) --
+static gkpack::Layout select_layout(const gk_set* h, const int32_t* ids, int64_t count) {
+  int64_t E = 0, P = 0;
+  for (int64_t k = 0; k < count; ++k) {
+    E += (int64_t)h->st[ids[k]].tab.size();
+    P += (int64_t)h->st[ids[k]].pend.size();
+  }
+  return gkpack::layout(count, E, P);
+}
+
+int gk_pack_select_bytes(gk_set* h, const int32_t* ids, int64_t count, int64_t* bytes, void* stream) {
+  (void)stream;
+  if (!bytes) return fail(GK_E_ARG, "bytes is null");
+  int rc = check_set(h);
+  if (!rc) rc = check_select(h, ids, count);
+  if (rc) return rc;
+  *bytes = (int64_t)select_layout(h, ids, count).total;
+  return GK_OK;
+}
+
+int gk_pack_select(gk_set* h, const int32_t* ids, int64_t count, void* buf, int64_t bytes, void* stream) {
+  (void)stream;
+  if (!buf) return fail(GK_E_ARG, "buf is null");
+  int rc = check_set(h);
+  if (!rc) rc = check_select(h, ids, count);
+  if (rc) return rc;
+  const gkpack::Layout L = select_layout(h, ids, count);
+  if (bytes < (int64_t)L.total)
+    return fail(GK_E_ARG, "packed state needs %lld bytes, the buffer has %lld", (long long)L.total, (long long)bytes);
+  gkpack::Header hd{};
+  hd.magic = gkpack::kMagic;
+  hd.version = gkpack::kVersion;
+  hd.header_bytes = sizeof(gkpack::Header);
+  hd.eps = h->eps;
+  hd.S = count;
+  hd.E = L.E;
+  hd.P = L.P;
+  hd.bytes = (int64_t)L.total;
+  memcpy(buf, &hd, sizeof(hd));
+  int64_t* const eo = gkpack::at<int64_t>(buf, L.eoffs);
+  int64_t* const po = gkpack::at<int64_t>(buf, L.poffs);
+  eo[0] = po[0] = 0;
+  for (int64_t k = 0; k < count; ++k) {
+    eo[k + 1] = eo[k] + (int64_t)h->st[ids[k]].tab.size();
+    po[k + 1] = po[k] + (int64_t)h->st[ids[k]].pend.size();
+  }
+  int64_t* const n = gkpack::at<int64_t>(buf, L.n);
+  double* const mn = gkpack::at<double>(buf, L.mn);
+  double* const mx = gkpack::at<double>(buf, L.mx);
+  double* const sum = gkpack::at<double>(buf, L.sum);
+  double* const avg = gkpack::at<double>(buf, L.avg);
+  double* const v = gkpack::at<double>(buf, L.v);
+  int32_t* const g = gkpack::at<int32_t>(buf, L.g);
+  int32_t* const d = gkpack::at<int32_t>(buf, L.d);
+  double* const pv = gkpack::at<double>(buf, L.pv);
+  // (read-only: rows of a repeated stream may be written in parallel)
+  parallel_for(count, h->threads, [&](int64_t k) {
+    const Stream& st = h->st[ids[k]];
+    n[k] = st.n;
+    mn[k] = st.mn;
+    mx[k] = st.mx;
+    sum[k] = st.sum;
+    avg[k] = st.avg;
+    for (size_t j = 0; j < st.tab.size(); ++j) {
+      v[eo[k] + (int64_t)j] = st.tab[j].v;
+      g[eo[k] + (int64_t)j] = (int32_t)st.tab[j].g;
+      d[eo[k] + (int64_t)j] = (int32_t)st.tab[j].d;
+    }
+    std::copy(st.pend.begin(), st.pend.end(), pv + po[k]);
+  });
+  return GK_OK;
+}
+
+int gk_unpack_select(gk_set* h, const int32_t* ids, int64_t count, const void* buf, void* stream) {
+  int rc = check_set(h);
+  if (!rc) rc = check_select_args(ids, count);
+  if (rc) return rc;
+  if (!buf) return fail(GK_E_ARG, "buf is null");
+  gkpack::Header hd{};
+  std::string err;
+  rc = gkpack::read_header<HostMem>(h, buf, &hd, stream, err, count);
+  if (rc) return err.empty() ? rc : fail(rc, "%s", err.c_str());
+  rc = check_select(h, ids, count);
+  if (rc) return rc;
+  std::vector<int32_t> uniq;
+  rc = distinct_ids(h, ids, count, uniq);
+  if (rc) return rc;
+  if ((int64_t)uniq.size() != count)
+    return fail(GK_E_ARG, "a stream id is listed more than once (two rows for one stream)");
+  const gkpack::Layout L = gkpack::layout(hd.S, hd.E, hd.P);
+  const int64_t* const eo = gkpack::at<int64_t>(buf, L.eoffs);
+  const int64_t* const po = gkpack::at<int64_t>(buf, L.poffs);
+  const int64_t* const n = gkpack::at<int64_t>(buf, L.n);
+  for (int64_t k = 0; k < count; ++k)
+    if (n[k] < 0 || po[k + 1] - po[k] > n[k] % h->P)
+      return fail(GK_E_ARG, "a packed stream holds more pending values than add() leaves (pending <= n %% %lld)",
+                  (long long)h->P);
+  const double* const mn = gkpack::at<double>(buf, L.mn);
+  const double* const mx = gkpack::at<double>(buf, L.mx);
+  const double* const sum = gkpack::at<double>(buf, L.sum);
+  const double* const avg = gkpack::at<double>(buf, L.avg);
+  const double* const v = gkpack::at<double>(buf, L.v);
+  const int32_t* const g = gkpack::at<int32_t>(buf, L.g);
+  const int32_t* const d = gkpack::at<int32_t>(buf, L.d);
+  const double* const pv = gkpack::at<double>(buf, L.pv);
+  // the new states are built beside the set and moved in whole: a stream
+  // never holds header words of one state and the table of the other
+  std::vector<Stream> fresh;
+  try {
+    fresh.resize((size_t)count);
+    parallel_for(count, h->threads, [&](int64_t k) {
+      Stream& st = fresh[(size_t)k];
+      st.n = n[k];
+      st.mn = mn[k];
+      st.mx = mx[k];
+      st.sum = sum[k];
+      st.avg = avg[k];
+      st.tab.reserve((size_t)(eo[k + 1] - eo[k]));
+      for (int64_t j = eo[k]; j < eo[k + 1]; ++j) st.tab.push_back(Rec{v[j], g[j], d[j]});
+      st.pend.assign(pv + po[k], pv + po[k + 1]);
+    });
+  } catch (...) {
+    return fail(GK_E_NOMEM, "unpack of %lld stream(s) failed", (long long)count);
+  }
+  for (int64_t k = 0; k < count; ++k) h->st[ids[k]] = std::move(fresh[(size_t)k]);
+  return GK_OK;
+}
+
 int gk_flush_period(const gk_set* h) { return h ? (int)std::min<int64_t>(h->P, INT32_MAX) : -1; }
 int gk_capacity(const gk_set* h, int cls) { return (h && cls == 0) ? INT32_MAX : -1; }  // unbounded, one class
 int64_t gk_num_promoted(const gk_set* h) { return h ? 0 : -1; }

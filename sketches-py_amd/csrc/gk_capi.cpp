@@ -1766,11 +1766,16 @@ int gk_stats(gk_set* h, int64_t* n, double* mn, double* mx, double* sum, double*
 static int64_t select_bitmap_words(const gk_set* h, bool want_list) { return want_list ? (h->S + 31) / 32 : 0; }
 
 // The selection scratch: k_select_check's control words, then (want_list) the
-// bitmap of listed streams and the flush list, both live at once.  Only grows;
-// the caller has synchronised `s` (nothing enqueued uses the old buffer).
-static int ensure_select_scratch(gk_set* h, int64_t count, bool want_list) {
-  const int64_t words =
+// bitmap of listed streams and the flush list, both live at once, then `extra`
+// words of the call's own (8-byte aligned: select_extra_at).  Only grows; the
+// caller has synchronised `s` (nothing enqueued uses the old buffer).
+static int64_t select_extra_at(const gk_set* h, int64_t count, bool want_list) {
+  const int64_t at =
       GK_SEL_WORDS + select_bitmap_words(h, want_list) + (want_list ? std::min<int64_t>(count, h->S) : 0);
+  return (at + 1) & ~(int64_t)1;
+}
+
+static int ensure_select_words(gk_set* h, int64_t words) {
   if (words <= h->sel_words) return GK_OK;
   h->sel_words = 0;
   if (!renew_dev(&h->d_sel, (size_t)words * sizeof(int32_t)))
@@ -1779,10 +1784,15 @@ static int ensure_select_scratch(gk_set* h, int64_t count, bool want_list) {
   return GK_OK;
 }
 
+static int ensure_select_scratch(gk_set* h, int64_t count, bool want_list, int64_t extra) {
+  return ensure_select_words(h, select_extra_at(h, count, want_list) + extra);
+}
+
 // what select_begin found: the listed streams with n > 0 and pending values (device; want_list)
 struct Selection {
   int32_t* list = nullptr;
   int64_t nflush = 0;
+  int32_t* extra = nullptr;  // the `extra` words asked of select_begin (8-byte aligned)
 };
 
 // Head of every selection call: the set and the id list are checked, then the
@@ -1792,17 +1802,18 @@ struct Selection {
 // nothing is mutated before its verdict has been read back.  The caller
 // returns at once on an error or count == 0.
 static int select_begin(gk_set* h, const int32_t* ids, int64_t count, bool want_list, void* stream, Selection* sel,
-                        const std::function<int()>& more = nullptr) {
+                        const std::function<int()>& more = nullptr, int64_t extra = 0) {
   int rc = check_set(h);
   if (!rc) rc = check_select_args(ids, count);
   if (!rc && more) rc = more();
   if (!rc) rc = gk_sync(h, stream);
   if (rc || count == 0) return rc;
   hipStream_t s = (hipStream_t)stream;
-  rc = ensure_select_scratch(h, count, want_list);
+  rc = ensure_select_scratch(h, count, want_list, extra);
   if (rc) return rc;
   const int64_t bm = select_bitmap_words(h, want_list);
   int32_t* const ctl = h->d_sel;
+  sel->extra = ctl + select_extra_at(h, count, want_list);
   uint32_t* const bitmap = reinterpret_cast<uint32_t*>(ctl + GK_SEL_WORDS);
   sel->list = want_list ? ctl + GK_SEL_WORDS + bm : nullptr;
   HIP_TRY(hipMemsetAsync(ctl, 0, (size_t)(GK_SEL_WORDS + bm) * sizeof(int32_t), s));
@@ -2310,7 +2321,7 @@ static int merge_self(gk_set* dst, hipStream_t s, void* stream) {
   if (rc) return rc;
   std::string err;
   gkpack::Header hd{};
-  rc = gkpack::read_header<DevMem>(dst->self_scratch, buf.p, &hd, stream, err);
+  rc = gkpack::read_header<DevMem>(dst->self_scratch, buf.p, &hd, stream, err, dst->S);
   if (!rc) rc = gkpack::import_packed<DevMem>(dst->self_scratch, buf.p, hd, stream);
   if (!rc) rc = gk_sync(dst->self_scratch, stream);
   if (rc) return (!err.empty()) ? fail(rc, "%s", err.c_str()) : rc;
@@ -2334,6 +2345,173 @@ int gk_fold_packed(gk_set* dst, const void* const* bufs, int nbufs, void* stream
   auto make = [&](gk_set** out) { return gk_create(dst->S, dst->eps, 0, dst->device, out); };
   rc = gkpack::fold<DevMem>(dst, bufs, nbufs, &dst->fold_scratch, make, stream, err);
   return (rc && !err.empty()) ? fail(rc, "%s", err.c_str()) : rc;
+}
+
+// ---- stream transfer: listed streams to and from a packed state -------------
+// (k_pack_sizes / k_pack_select / k_unpack_check / k_unpack_select)
+
+// gk_pack_select_bytes (need_out given: only the size) and gk_pack_select.
+// The sizes go straight into the buffer's eoffs / poffs sections -- their
+// positions depend only on `count` -- and are scanned there on the device;
+// the host reads back the two totals only (layout and header need them).
+static int pack_select_impl(gk_set* h, const int32_t* ids, int64_t count, void* buf, int64_t bytes, int64_t* need_out,
+                            void* stream) {
+  Selection sel;
+  const int64_t nsum = gk_scan_sums(std::max<int64_t>(count, 0) + 1);
+  int rc = select_begin(h, ids, count, false, stream, &sel, nullptr, 4 + 2 * nsum);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const gkpack::Layout L0 = gkpack::layout(count, 0, 0);
+  const bool sized = !need_out && bytes >= (int64_t)L0.total;  // the offset sections lie inside the buffer
+  unsigned long long* const totals = reinterpret_cast<unsigned long long*>(sel.extra);
+  int64_t E = 0, P = 0;
+  if (count > 0) {
+    HIP_TRY(hipMemsetAsync(totals, 0, 2 * sizeof(unsigned long long), s));
+    HIP_TRY(gk_launch_pack_sizes(h->st, ids, count, sized ? gkpack::at<int64_t>(buf, L0.eoffs) : nullptr,
+                                 sized ? gkpack::at<int64_t>(buf, L0.poffs) : nullptr, totals, s));
+    HIP_TRY(hipMemcpyAsync(h->h_ovf, totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    E = reinterpret_cast<const int64_t*>(h->h_ovf)[0];
+    P = reinterpret_cast<const int64_t*>(h->h_ovf)[1];
+  }
+  const gkpack::Layout L = gkpack::layout(count, E, P);
+  if (need_out) {
+    *need_out = (int64_t)L.total;
+    return GK_OK;
+  }
+  if (bytes < (int64_t)L.total)
+    return fail(GK_E_ARG, "packed state needs %lld bytes, the buffer has %lld", (long long)L.total, (long long)bytes);
+  gkpack::Header hd{};
+  hd.magic = gkpack::kMagic;
+  hd.version = gkpack::kVersion;
+  hd.header_bytes = sizeof(gkpack::Header);
+  hd.eps = h->eps;
+  hd.S = count;
+  hd.E = E;
+  hd.P = P;
+  hd.bytes = (int64_t)L.total;
+  rc = DevMem::from_host(buf, &hd, sizeof(hd), stream);
+  if (rc) return rc;
+  if (count == 0) {
+    HIP_TRY(hipMemsetAsync(gkpack::at<int64_t>(buf, L.eoffs), 0, sizeof(int64_t), s));
+    HIP_TRY(hipMemsetAsync(gkpack::at<int64_t>(buf, L.poffs), 0, sizeof(int64_t), s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return GK_OK;
+  }
+  int64_t* const eo = gkpack::at<int64_t>(buf, L.eoffs);
+  int64_t* const po = gkpack::at<int64_t>(buf, L.poffs);
+  HIP_TRY(gk_launch_scan_i64(eo, count + 1, totals + 2, s));
+  HIP_TRY(gk_launch_scan_i64(po, count + 1, totals + 2, s));
+  const GKSelectStats o{gkpack::at<int64_t>(buf, L.n),    gkpack::at<double>(buf, L.mn), gkpack::at<double>(buf, L.mx),
+                        gkpack::at<double>(buf, L.sum), gkpack::at<double>(buf, L.avg), nullptr,
+                        nullptr};
+  HIP_TRY(gk_launch_select_stats(h->st, ids, count, o, s));
+  HIP_TRY(gk_launch_pack_select(h->st, ids, count, eo, po, gkpack::at<double>(buf, L.v), gkpack::at<int32_t>(buf, L.g),
+                                gkpack::at<int32_t>(buf, L.d), gkpack::at<double>(buf, L.pv), s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return GK_OK;
+}
+
+int gk_pack_select_bytes(gk_set* h, const int32_t* ids, int64_t count, int64_t* bytes, void* stream) {
+  if (!bytes) return fail(GK_E_ARG, "bytes is null");
+  return pack_select_impl(h, ids, count, nullptr, 0, bytes, stream);
+}
+
+int gk_pack_select(gk_set* h, const int32_t* ids, int64_t count, void* buf, int64_t bytes, void* stream) {
+  if (!buf) return fail(GK_E_ARG, "buf is null");
+  return pack_select_impl(h, ids, count, buf, bytes, nullptr, stream);
+}
+
+int gk_unpack_select(gk_set* h, const int32_t* ids, int64_t count, const void* buf, void* stream) {
+  int rc = check_set(h);
+  if (!rc) rc = check_select_args(ids, count);
+  if (rc) return rc;
+  if (!buf) return fail(GK_E_ARG, "buf is null");
+  rc = gk_sync(h, stream);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  gkpack::Header hd{};
+  std::string err;
+  if (count == 0) {  // the buffer is still validated (header and its one-entry offset tables)
+    rc = gkpack::read_header<DevMem>(h, buf, &hd, stream, err, 0);
+    return (rc && !err.empty()) ? fail(rc, "%s", err.c_str()) : rc;
+  }
+  rc = DevMem::to_host(&hd, buf, sizeof(hd), stream);
+  if (rc) return rc;
+  rc = gkpack::check_header(hd, h->eps, count, err);
+  if (rc) return fail(rc, "%s", err.c_str());
+  const gkpack::Layout L = gkpack::layout(hd.S, hd.E, hd.P);
+  const GKPacked pk{gkpack::at<int64_t>(buf, L.n),     gkpack::at<double>(buf, L.mn),    gkpack::at<double>(buf, L.mx),
+                    gkpack::at<double>(buf, L.sum),    gkpack::at<double>(buf, L.avg),   gkpack::at<int64_t>(buf, L.eoffs),
+                    gkpack::at<int64_t>(buf, L.poffs), gkpack::at<double>(buf, L.v),     gkpack::at<int32_t>(buf, L.g),
+                    gkpack::at<int32_t>(buf, L.d),     gkpack::at<double>(buf, L.pv),    hd.E,
+                    hd.P};
+  // scratch: control words, the bitmap of listed streams, the overflow rows
+  const int64_t bm = (h->S + 31) / 32;
+  rc = ensure_select_words(h, GK_UNP_WORDS + bm + std::min<int64_t>(count, h->S));
+  if (rc) return rc;
+  int32_t* const ctl = h->d_sel;
+  uint32_t* const bitmap = reinterpret_cast<uint32_t*>(ctl + GK_UNP_WORDS);
+  int32_t* const rows = ctl + GK_UNP_WORDS + bm;
+  HIP_TRY(hipMemsetAsync(ctl, 0, (size_t)(GK_UNP_WORDS + bm) * sizeof(int32_t), s));
+  HIP_TRY(gk_launch_unpack_check(h->st, ids, count, pk, ctl, bitmap, s));
+  HIP_TRY(hipMemcpyAsync(h->h_ovf, ctl, GK_UNP_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const int bad = h->h_ovf[GK_UNP_BAD];
+  if (bad & 4) return fail(GK_E_FORMAT, "%s", gkpack::kBadOffsets);
+  if (bad & 1) {
+    const int64_t first = count - (int64_t)(uint32_t)h->h_ovf[GK_UNP_FIRST];
+    int32_t id = 0;
+    HIP_TRY(hipMemcpy(&id, ids + first, sizeof(int32_t), hipMemcpyDeviceToHost));
+    return fail(GK_E_ARG, "ids[%lld] = %d lies outside [0, %lld)", (long long)first, id, (long long)h->S);
+  }
+  if (bad & 2) return fail(GK_E_ARG, "a stream id is listed more than once (two rows for one stream)");
+  if (bad & 8)
+    return fail(GK_E_ARG, "a packed stream holds more pending values than add() leaves (pending <= n %% %d)", h->P);
+  const int last = h->st.nclass - 1;
+  if (h->h_ovf[GK_UNP_MAXE] > h->st.cap[last] - 1)
+    return fail(GK_E_OVERFLOW, "a packed table of %d entries exceeds the last capacity class (%d entries)",
+                h->h_ovf[GK_UNP_MAXE], h->st.cap[last] - 1);
+  // the arenas grow BEFORE the first write: GK_E_NOMEM leaves every stream as it was
+  int64_t need[GK_MAX_CLASSES] = {}, moving = 0;
+  for (int t = 1; t <= last; ++t) moving += need[t] = h->h_ovf[GK_UNP_NEED + t];
+  for (int t = 1; t <= last; ++t) {
+    if (!need[t]) continue;
+    rc = grow_class(h, t, (int64_t)h->st.alloc[t] + need[t], s);
+    if (rc) return rc;
+  }
+  GKUnpackOvf ov{};
+  ov.count = h->d_ovfc;
+  ov.stuck = ctl + GK_UNP_STUCK;
+  int64_t at = 0;
+  for (int t = 1; t <= last; ++t) {
+    ov.list[t] = ovf_list(h, t);
+    ov.rows[t] = rows + at;
+    at += need[t];
+  }
+  h->ctr_clean = false;  // (the overflow counts are words of the per-call block)
+  HIP_TRY(hipMemsetAsync(h->d_ovfc, 0, kRounds * sizeof(int32_t), s));
+  HIP_TRY(gk_launch_unpack_select(h->st, ids, nullptr, count, pk, ov, s));
+  if (moving == 0) {
+    HIP_TRY(hipStreamSynchronize(s));
+    return GK_OK;
+  }
+  // the rows whose table outgrew their stream's class: the streams move to
+  // the class that holds it (k_promote_dev copies the old table, about to be
+  // overwritten), then their rows are installed
+  const GKPoolDev pool = pool_args(h);
+  h->no_members = false;
+  for (int t = 1; t <= last; ++t) {
+    if (!need[t]) continue;
+    HIP_TRY(gk_launch_promote_dev(h->st, ovf_count(h, t), ovf_list(h, t), t, pool, s));
+    HIP_TRY(gk_launch_unpack_select(h->st, ids, ov.rows[t], need[t], pk, ov, s));
+  }
+  HIP_TRY(hipMemcpyAsync(h->h_ovf, ov.stuck, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  rc = select_end(h, s);
+  if (rc) return rc;
+  if (h->h_ovf[0] != 0)
+    return fail(GK_E_OVERFLOW, "%d packed stream(s) found no slot in a capacity class and keep their state", h->h_ovf[0]);
+  return GK_OK;
 }
 
 int64_t gk_num_streams(const gk_set* h) { return h ? h->S : -1; }

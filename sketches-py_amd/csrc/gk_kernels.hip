@@ -21,6 +21,9 @@
 //   k_rank       (no gk line: the reference has no rank())  wave per row: bounds on
 //                           the count of values <= x from the flushed table
 //   k_export / k_import / k_reset: state movement
+//   k_pack_* / k_unpack_*   (gk:21-29, the whole state)  listed streams to and from a
+//                           packed state: sizes + totals, wave per row gather; one
+//                           checking pass, wave per row install (no flush)
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
@@ -5489,6 +5492,179 @@ __global__ void k_import(GKState st, const int64_t* __restrict__ offs, const dou
   }
 }
 
+// ---- stream transfer (gk_pack_select / gk_unpack_select): a LIST of streams
+// to and from a GKPACK01 buffer (gk_pack.h), row k of the buffer = stream
+// ids[k].  Neither direction flushes.
+//
+// k_pack_sizes: the two totals (sum of E and of pend over the rows, added to
+// totals[0] / totals[1], zeroed by the caller) and, eoffs != NULL, the sizes as
+// int64 into eoffs / poffs[0 .. count) with a 0 at [count] -- the input of the
+// in-place exclusive scan (gk_launch_scan_i64) that turns them into offsets.
+__global__ __launch_bounds__(256) void k_pack_sizes(GKState st, const int32_t* __restrict__ ids, int64_t count,
+                                                    int64_t* __restrict__ eoffs, int64_t* __restrict__ poffs,
+                                                    unsigned long long* __restrict__ totals) {
+  const int lane = threadIdx.x & 63;
+  const int64_t step = (int64_t)gridDim.x * blockDim.x;
+  unsigned long long te = 0, tp = 0;
+  for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k <= count; k += step) {  // ([count]: the 0)
+    int64_t e = 0, p = 0;
+    if (k < count) {
+      const int64_t s = ids[k];
+      e = st.E[s];
+      p = st.pend[s];
+    }
+    if (eoffs) {
+      eoffs[k] = e;
+      poffs[k] = p;
+    }
+    te += (unsigned long long)e;
+    tp += (unsigned long long)p;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    te += __shfl_xor(te, o, 64);
+    tp += __shfl_xor(tp, o, 64);
+  }
+  if (lane == 0 && (te | tp)) {
+    if (te) atomicAdd(&totals[0], te);
+    if (tp) atomicAdd(&totals[1], tp);
+  }
+}
+
+// k_pack_select: one wave per row; the table leaves as 16-byte records
+// (int4: v low, v high, g, delta) into v / g / d at eoffs[k], the pending
+// values in insertion order into pv at poffs[k].  Reads the set only.  (A row
+// with a very long table is walked by its one wave.)
+__global__ __launch_bounds__(256) void k_pack_select(GKState st, const int32_t* __restrict__ ids, int64_t count,
+                                                     const int64_t* __restrict__ eoffs,
+                                                     const int64_t* __restrict__ poffs, double* __restrict__ v,
+                                                     int32_t* __restrict__ g, int32_t* __restrict__ d,
+                                                     double* __restrict__ pv) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wid = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwv = (int64_t)gridDim.x * 4;
+  for (int64_t k = wid; k < count; k += nwv) {
+    const int64_t s = ids[k];
+    const int4* __restrict__ t4 = (const int4*)gk_table_ptr(st, s);
+    const int E = st.E[s];
+    const int p = st.pend[s];
+    const int64_t o = eoffs[k], po = poffs[k];
+    for (int j = lane; j < E; j += 64) {
+      const int4 rc = t4[j];
+      v[o + j] = __hiloint2double(rc.y, rc.x);
+      g[o + j] = rc.z;
+      d[o + j] = rc.w;
+    }
+    const double* __restrict__ pb = st.pbuf + s * (int64_t)st.pmax;
+    for (int j = lane; j < p; j += 64) pv[po + j] = pb[j];
+  }
+}
+
+// The class a stream in class c moves to for a table of E entries: the first
+// above c that holds it (a class keeps one slot for padding, as k_import's
+// rule); nclass when none does.
+__device__ __forceinline__ int unpack_target(const GKState& st, int c, int64_t E) {
+  int t = c + 1;
+  while (t < st.nclass && E > (int64_t)st.cap[t] - 1) ++t;
+  return t;
+}
+
+// k_unpack_check: every refusal of gk_unpack_select that needs the device, in
+// one pass that mutates no stream state; ctl (GK_UNP_WORDS words) and the
+// bitmap ((S + 31) / 32 words) are zeroed by the caller, who reads ctl back
+// before anything is written.  Row k:
+//  * ids[k] outside [0, S): bit 1 of ctl[GK_UNP_BAD], count - k into the max
+//    ctl[GK_UNP_FIRST] (k_select_check's encoding of the FIRST bad index);
+//  * ids[k] listed before (bitmap): bit 2;
+//  * offsets not monotone from 0 to the header's totals: bit 4;
+//  * a pending count that add() cannot leave (k_check_pending's rule): bit 8;
+//  * its table size into the max ctl[GK_UNP_MAXE], and, when the table does
+//    not fit the stream's class, one more slot needed in the class it moves to
+//    (ctl[GK_UNP_NEED + t]) -- the host grows the arenas from these before the
+//    first write.
+__global__ void k_unpack_check(GKState st, const int32_t* __restrict__ ids, int64_t count, GKPacked pk,
+                               int32_t* __restrict__ ctl, uint32_t* __restrict__ bitmap) {
+  const int64_t step = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += step) {
+    int bad = 0;
+    const int64_t e0 = pk.eoffs[k], e1 = pk.eoffs[k + 1], p0 = pk.poffs[k], p1 = pk.poffs[k + 1];
+    if (e1 < e0 || p1 < p0 || (k == 0 && (e0 != 0 || p0 != 0)) || (k == count - 1 && (e1 != pk.E || p1 != pk.P)))
+      bad |= 4;
+    const int64_t ns = pk.n[k], p = p1 - p0, E = e1 - e0;
+    if (!(bad & 4) && (ns < 0 || p > ns % st.P)) bad |= 8;
+    const int64_t s = ids[k];
+    if (s < 0 || s >= st.S) {
+      bad |= 1;
+      atomicMax(reinterpret_cast<uint32_t*>(&ctl[GK_UNP_FIRST]), (uint32_t)(count - k));
+    } else {
+      const uint32_t bit = 1u << (s & 31);
+      if (atomicOr(&bitmap[s >> 5], bit) & bit) bad |= 2;
+      if (!(bad & 4)) {
+        atomicMax(&ctl[GK_UNP_MAXE], (int32_t)(E > INT32_MAX ? INT32_MAX : E));
+        const int c = st.cls[s];
+        if (E > (int64_t)st.cap[c] - 1) {
+          const int t = unpack_target(st, c, E);
+          if (t < st.nclass) atomicAdd(&ctl[GK_UNP_NEED + t], 1);
+        }
+      }
+    }
+    if (bad) atomicOr(&ctl[GK_UNP_BAD], bad);
+  }
+}
+
+// k_unpack_select: one wave per row k (rows == NULL: every row of the buffer;
+// else rows[0 .. nrows)).  A row whose table fits its stream's class installs
+// the table, the pending values and ALL header words in this one pass -- a
+// stream therefore holds its complete old or its complete new state, whatever
+// happens to other rows.  A row that does not fit joins the overflow list of
+// the class t it moves to: its stream id into ov.list[t] (k_promote_dev's
+// input) and the row into ov.rows[t] at the same position, ov.count[t] of
+// them; the host promotes the listed streams and launches again over
+// ov.rows[t].  (On the relaunch every row fits; one that still does not --
+// its promotion found no slot -- is counted in *ov.stuck and left alone.)
+__global__ __launch_bounds__(256) void k_unpack_select(GKState st, const int32_t* __restrict__ ids,
+                                                       const int32_t* __restrict__ rows, int64_t nrows, GKPacked pk,
+                                                       GKUnpackOvf ov) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wid = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwv = (int64_t)gridDim.x * 4;
+  for (int64_t w = wid; w < nrows; w += nwv) {
+    const int64_t k = rows ? (int64_t)rows[w] : w;
+    const int64_t s = ids[k];
+    const int64_t o = pk.eoffs[k], po = pk.poffs[k];
+    const int64_t E = pk.eoffs[k + 1] - o;
+    const int p = (int)(pk.poffs[k + 1] - po);
+    const int c = st.cls[s];
+    if (E > (int64_t)st.cap[c] - 1) {
+      if (lane == 0) {
+        const int t = unpack_target(st, c, E);
+        if (rows || t >= st.nclass) {
+          atomicAdd(ov.stuck, 1);
+        } else {
+          const int i = atomicAdd(&ov.count[t], 1);
+          ov.list[t][i] = (int32_t)s;
+          ov.rows[t][i] = (int32_t)k;
+        }
+      }
+      continue;
+    }
+    int4* __restrict__ t4 = (int4*)gk_table_ptr(st, s);
+    for (int j = lane; j < (int)E; j += 64) {
+      const double x = pk.v[o + j];
+      t4[j] = make_int4(__double2loint(x), __double2hiint(x), pk.g[o + j], pk.d[o + j]);
+    }
+    double* __restrict__ pb = st.pbuf + s * (int64_t)st.pmax;
+    for (int j = lane; j < p; j += 64) pb[j] = pk.pv[po + j];
+    if (lane == 0) {
+      st.E[s] = (int32_t)E;
+      st.pend[s] = p;
+      st.n[s] = pk.n[k];
+      st.mn[s] = pk.mn[k];
+      st.mx[s] = pk.mx[k];
+      st.sum[s] = pk.sum[k];
+      st.avg[s] = pk.avg[k];
+    }
+  }
+}
+
 // move each listed stream's table into its (already assigned) slot of class `ncls`
 __global__ void k_promote(GKState st, const int32_t* __restrict__ list, int64_t count,
                           const int32_t* __restrict__ slots, int ncls) {
@@ -6041,6 +6217,38 @@ hipError_t gk_launch_import(const GKState& st, const int64_t* offs, const double
   if (st.S <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_import, dim3((unsigned)wave_grid(st.S)), dim3(256), 0, stream, st, offs, v, g, d,
                      poffs, pv, ovf_count, ovf_list);
+  return hipGetLastError();
+}
+
+hipError_t gk_launch_pack_sizes(const GKState& st, const int32_t* ids, int64_t count, int64_t* eoffs, int64_t* poffs,
+                                unsigned long long* totals, hipStream_t stream) {
+  if (count < 0) return hipSuccess;
+  hipLaunchKernelGGL(k_pack_sizes, dim3(select_grid(count + 1)), dim3(256), 0, stream, st, ids, count, eoffs, poffs,
+                     totals);
+  return hipGetLastError();
+}
+
+hipError_t gk_launch_pack_select(const GKState& st, const int32_t* ids, int64_t count, const int64_t* eoffs,
+                                 const int64_t* poffs, double* v, int32_t* g, int32_t* d, double* pv,
+                                 hipStream_t stream) {
+  if (count <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_pack_select, dim3((unsigned)wave_grid(count)), dim3(256), 0, stream, st, ids, count, eoffs,
+                     poffs, v, g, d, pv);
+  return hipGetLastError();
+}
+
+hipError_t gk_launch_unpack_check(const GKState& st, const int32_t* ids, int64_t count, const GKPacked& pk,
+                                  int32_t* ctl, uint32_t* bitmap, hipStream_t stream) {
+  if (count <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_unpack_check, dim3(select_grid(count)), dim3(256), 0, stream, st, ids, count, pk, ctl, bitmap);
+  return hipGetLastError();
+}
+
+hipError_t gk_launch_unpack_select(const GKState& st, const int32_t* ids, const int32_t* rows, int64_t nrows,
+                                   const GKPacked& pk, const GKUnpackOvf& ov, hipStream_t stream) {
+  if (nrows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_unpack_select, dim3((unsigned)wave_grid(nrows)), dim3(256), 0, stream, st, ids, rows, nrows,
+                     pk, ov);
   return hipGetLastError();
 }
 

@@ -72,7 +72,9 @@ __global__ void k_group_verdict(const int32_t* __restrict__ ids, int64_t count, 
 
 // ---- exclusive scan of a[0..n) in place: tile sums, scan of the sums by one
 // workgroup, tile scan + base.  T = uint32_t (digit counts: every partial sum
-// is at most count < 2^31).
+// is at most count < 2^31) or int64_t (gk_launch_scan_i64: non-negative sizes).
+// call: the keyed call's control words (a void call's scan does nothing), or
+// NULL.
 template <typename T>
 __device__ __forceinline__ void load_tile(const T* a, int64_t n, int64_t base, T (&v)[SC_ITEMS]) {
 #pragma unroll
@@ -108,7 +110,7 @@ template <typename T>
 __global__ __launch_bounds__(SC_THREADS) void k_scan_sums(const T* __restrict__ a, int64_t n, u64* __restrict__ sums,
                                                           const u64* __restrict__ call) {
   __shared__ u64 lds[SC_THREADS / 64];
-  if (call[GK_KG_BAD]) return;
+  if (call && call[GK_KG_BAD]) return;
   T v[SC_ITEMS];
   load_tile(a, n, (int64_t)blockIdx.x * SC_TILE + (int64_t)threadIdx.x * SC_ITEMS, v);
   u64 x = 0;
@@ -123,7 +125,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_scan_sums(const T* __restrict__ 
 __global__ __launch_bounds__(1024) void k_scan_mid(u64* __restrict__ sums, int64_t nb, const u64* __restrict__ call,
                                                    u64* __restrict__ total_out) {
   __shared__ u64 lds[1024 / 64];
-  if (call[GK_KG_BAD]) return;
+  if (call && call[GK_KG_BAD]) return;
   u64 carry = 0;
   for (int64_t base = 0; base < nb; base += 1024) {
     const int64_t i = base + threadIdx.x;
@@ -141,7 +143,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_scan_apply(T* __restrict__ a, in
                                                            const u64* __restrict__ call) {
   __shared__ u64 lds[SC_THREADS / 64];
   const int64_t base = (int64_t)blockIdx.x * SC_TILE + (int64_t)threadIdx.x * SC_ITEMS;
-  if (call[GK_KG_BAD]) return;
+  if (call && call[GK_KG_BAD]) return;
   T v[SC_ITEMS];
   load_tile(a, n, base, v);
   u64 x = 0;
@@ -342,16 +344,21 @@ __global__ __launch_bounds__(256) void k_group_offsets(const int32_t* __restrict
 }
 
 // total_out (may be NULL): where the array's sum goes
-hipError_t scan_in_place(uint32_t* a, int64_t n, u64* sums, const u64* call, u64* total_out, hipStream_t s) {
+template <typename T>
+hipError_t scan_in_place(T* a, int64_t n, u64* sums, const u64* call, u64* total_out, hipStream_t s) {
   const int64_t nb = (n + SC_TILE - 1) / SC_TILE;
   if (nb <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_scan_sums<uint32_t>, dim3((unsigned)nb), dim3(SC_THREADS), 0, s, a, n, sums, call);
+  hipLaunchKernelGGL(k_scan_sums<T>, dim3((unsigned)nb), dim3(SC_THREADS), 0, s, a, n, sums, call);
   hipLaunchKernelGGL(k_scan_mid, dim3(1), dim3(1024), 0, s, sums, nb, call, total_out);
-  hipLaunchKernelGGL(k_scan_apply<uint32_t>, dim3((unsigned)nb), dim3(SC_THREADS), 0, s, a, n, sums, call);
+  hipLaunchKernelGGL(k_scan_apply<T>, dim3((unsigned)nb), dim3(SC_THREADS), 0, s, a, n, sums, call);
   return hipGetLastError();
 }
 
 }  // namespace
+
+hipError_t gk_launch_scan_i64(int64_t* a, int64_t n, unsigned long long* sums, hipStream_t stream) {
+  return scan_in_place<int64_t>(a, n, sums, nullptr, nullptr, stream);
+}
 
 int gk_group_passes(int64_t S) {
   int bits = 0;

@@ -214,6 +214,62 @@ struct GKSelectStats {
 };
 hipError_t gk_launch_select_stats(const GKState& st, const int32_t* ids, int64_t count, const GKSelectStats& o,
                                   hipStream_t stream);
+// ---- stream transfer (gk_pack_select / gk_unpack_select): listed streams to
+// and from a GKPACK01 buffer (gk_pack.h); row k of the buffer = stream ids[k] ----
+// Exclusive scan in place of n non-negative int64 values (gk_keyed.hip's
+// k_scan_sums / k_scan_mid / k_scan_apply); sums: gk_scan_sums(n) words.
+inline int64_t gk_scan_sums(int64_t n) { return (n + 2047) / 2048; }
+hipError_t gk_launch_scan_i64(int64_t* a, int64_t n, unsigned long long* sums, hipStream_t stream);
+// totals[0] += the rows' table sizes, totals[1] += their pending counts (zeroed
+// by the caller); eoffs != NULL: the sizes as int64 into eoffs / poffs[0 .. count)
+// and a 0 into [count] (count + 1 entries each), for the scan above
+hipError_t gk_launch_pack_sizes(const GKState& st, const int32_t* ids, int64_t count, int64_t* eoffs, int64_t* poffs,
+                                unsigned long long* totals, hipStream_t stream);
+// tables to v / g / d at eoffs[k], pending values to pv at poffs[k] (k_pack_select)
+hipError_t gk_launch_pack_select(const GKState& st, const int32_t* ids, int64_t count, const int64_t* eoffs,
+                                 const int64_t* poffs, double* v, int32_t* g, int32_t* d, double* pv,
+                                 hipStream_t stream);
+// the sections of a packed buffer (device) and its header's totals
+struct GKPacked {
+  const int64_t* n;
+  const double* mn;
+  const double* mx;
+  const double* sum;
+  const double* avg;
+  const int64_t* eoffs;
+  const int64_t* poffs;
+  const double* v;
+  const int32_t* g;
+  const int32_t* d;
+  const double* pv;
+  int64_t E, P;
+};
+// Control words of k_unpack_check (zeroed by the caller with the bitmap):
+#define GK_UNP_BAD 0    // bit 1 an id outside [0, S), 2 an id listed twice, 4 offsets not monotone, 8 pending rule
+#define GK_UNP_FIRST 1  // count minus the first bad index (as GK_SEL_FIRST)
+#define GK_UNP_MAXE 2   // the largest table of the buffer
+#define GK_UNP_STUCK 3  // k_unpack_select: rows that found no class (none after a successful check)
+#define GK_UNP_NEED 4   // [4 + t]: rows that move to class t (t = 1 .. GK_MAX_CLASSES - 1)
+#define GK_UNP_WORDS 8
+static_assert(GK_UNP_NEED + GK_MAX_CLASSES <= GK_UNP_WORDS, "one need count per class");
+// every device-side refusal of gk_unpack_select in one pass that mutates
+// nothing (bitmap: (S + 31) / 32 zeroed words)
+hipError_t gk_launch_unpack_check(const GKState& st, const int32_t* ids, int64_t count, const GKPacked& pk,
+                                  int32_t* ctl, uint32_t* bitmap, hipStream_t stream);
+// overflow lists of k_unpack_select by the class t a row moves to: count[t]
+// rows, their stream ids in list[t] (k_promote_dev's input) and the rows
+// themselves in rows[t], same positions; stuck: ctl + GK_UNP_STUCK
+struct GKUnpackOvf {
+  int32_t* count;
+  int32_t* list[GK_MAX_CLASSES];
+  int32_t* rows[GK_MAX_CLASSES];
+  int32_t* stuck;
+};
+// installs the rows that fit their stream's class (table, pending values and
+// header words in one pass); rows NULL: every row of the buffer (nrows = count),
+// the others go to `ov`; rows given: those rows (after their promotion)
+hipError_t gk_launch_unpack_select(const GKState& st, const int32_t* ids, const int32_t* rows, int64_t nrows,
+                                   const GKPacked& pk, const GKUnpackOvf& ov, hipStream_t stream);
 // ---- keyed ingest (gk_keyed.hip): stable group-by of (id, value) samples ----
 // An LSD radix partition by stream id, GK_GROUP_BITS per pass over tiles of
 // GK_GROUP_TILE samples (one workgroup each).  The set owns the scratch:
@@ -229,6 +285,7 @@ struct GKGroupScratch {
 #define GK_GROUP_BITS 8
 #define GK_GROUP_TILE 4096
 #define GK_GROUP_SCAN_TILE 2048
+static_assert(GK_GROUP_SCAN_TILE == 2048, "gk_scan_sums counts tiles of 2048");
 #define GK_KG_BAD 0     // ids >= S in this call
 #define GK_KG_BADKEY 1  // max of (count - index) over them
 #define GK_KG_KEPT 2    // samples with an id in [0, S)

@@ -154,38 +154,50 @@ int pack(gk_set* set, int32_t* esz, int32_t* psz, void* buf, int64_t bytes, void
   return rc;
 }
 
-// Header of a packed buffer, validated against `dst`.
-template <class Mem>
-int read_header(gk_set* dst, const void* buf, Header* h, void* stream, std::string& err) {
-  int rc = Mem::to_host(h, buf, sizeof(Header), stream);
-  if (rc) return rc;
-  if (h->magic != kMagic || h->header_bytes != sizeof(Header)) {
+// The header's own fields against the receiving set's eps and the stream count
+// the caller expects (a whole set: gk_num_streams; gk_unpack_select: `count`).
+// Host-side; shared by both engines.
+inline int check_header(const Header& h, double eps, int64_t expect_S, std::string& err) {
+  if (h.magic != kMagic || h.header_bytes != sizeof(Header)) {
     err = "not a packed GK state";
     return GK_E_FORMAT;
   }
-  if (h->version != kVersion) {
-    err = "packed GK state version " + std::to_string(h->version) + " is not supported";
+  if (h.version != kVersion) {
+    err = "packed GK state version " + std::to_string(h.version) + " is not supported";
     return GK_E_FORMAT;
   }
-  if (h->eps != gk_eps(dst)) {  // gk:118-119
+  if (h.eps != eps) {  // gk:118-119
     err = "Cannot merge two GKArrays with different epsilon values";
     return GK_E_EPS_MISMATCH;
   }
-  if (h->S != gk_num_streams(dst)) {
-    err = "packed state holds " + std::to_string(h->S) + " streams, the set has " +
-          std::to_string(gk_num_streams(dst));
+  if (h.S != expect_S) {
+    err = "packed state holds " + std::to_string(h.S) + " streams, " + std::to_string(expect_S) + " are expected";
     return GK_E_ARG;
   }
-  // sizes and offsets must be internally consistent before gk_import copies
-  // anything (a corrupt header or offset table is refused).  The buffer's
-  // own length is not known here (gk_fold_packed takes bare pointers): the
-  // caller guarantees each buffer holds the header's `bytes` (gk_capi.h) --
-  // a buffer truncated after an intact header and offset table is not caught
-  if (h->E < 0 || h->P < 0 || h->E > ((int64_t)1 << 40) || h->P > ((int64_t)1 << 40) ||
-      h->bytes != (int64_t)layout(h->S, h->E, h->P).total) {
+  // sizes and offsets must be internally consistent before anything is
+  // copied (a corrupt header or offset table is refused).  The buffer's
+  // own length is not known here (gk_fold_packed and gk_unpack_select take
+  // bare pointers): the caller guarantees each buffer holds the header's
+  // `bytes` (gk_capi.h) -- a buffer truncated after an intact header and
+  // offset table is not caught
+  if (h.E < 0 || h.P < 0 || h.E > ((int64_t)1 << 40) || h.P > ((int64_t)1 << 40) ||
+      h.bytes != (int64_t)layout(h.S, h.E, h.P).total) {
     err = "packed state header is inconsistent (sizes / byte count)";
     return GK_E_FORMAT;
   }
+  return GK_OK;
+}
+
+constexpr const char* kBadOffsets = "packed state offsets are not monotone from 0 to the header's totals";
+
+// Header of a packed buffer of `expect_S` streams, validated against `dst`'s
+// eps, and its two offset tables (read to the host).
+template <class Mem>
+int read_header(gk_set* dst, const void* buf, Header* h, void* stream, std::string& err, int64_t expect_S) {
+  int rc = Mem::to_host(h, buf, sizeof(Header), stream);
+  if (rc) return rc;
+  rc = check_header(*h, gk_eps(dst), expect_S, err);
+  if (rc) return rc;
   const Layout L = layout(h->S, h->E, h->P);
   std::vector<int64_t> eo(h->S + 1), po(h->S + 1);
   rc = Mem::to_host(eo.data(), at<int64_t>(buf, L.eoffs), 8 * (size_t)(h->S + 1), stream);
@@ -194,7 +206,7 @@ int read_header(gk_set* dst, const void* buf, Header* h, void* stream, std::stri
   bool ok = eo[0] == 0 && po[0] == 0 && eo[h->S] == h->E && po[h->S] == h->P;
   for (int64_t s = 0; ok && s < h->S; ++s) ok = eo[s + 1] >= eo[s] && po[s + 1] >= po[s];
   if (!ok) {
-    err = "packed state offsets are not monotone from 0 to the header's totals";
+    err = kBadOffsets;
     return GK_E_FORMAT;
   }
   return GK_OK;
@@ -226,7 +238,7 @@ int fold(gk_set* dst, const void* const* bufs, int nbufs, gk_set** scratch, Make
       err = "packed state " + std::to_string(r) + " is null";
       return GK_E_ARG;
     }
-    int rc = read_header<Mem>(dst, bufs[r], &hs[r], stream, err);
+    int rc = read_header<Mem>(dst, bufs[r], &hs[r], stream, err, gk_num_streams(dst));
     if (rc) return rc;
   }
   int rc = import_packed<Mem>(dst, bufs[0], hs[0], stream);

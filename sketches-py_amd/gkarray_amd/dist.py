@@ -33,7 +33,7 @@ import torch.distributed as dist
 
 __all__ = ["stream_range", "balanced_assignment", "pack_state", "unpack_state", "all_gather_varlen",
            "allgather_states", "alltoall_states", "slice_state", "concat_states", "fold_states",
-           "merge_row_shards", "RowShardMerger", "allgather_packed", "fold_packed_allgather"]
+           "merge_row_shards", "RowShardMerger", "allgather_packed", "fold_packed_allgather", "exchange_streams"]
 
 _F64 = ("v", "pv", "min", "max", "sum", "avg")
 _I64 = ("offs", "poffs", "n")
@@ -393,6 +393,56 @@ class RowShardMerger:
                               n=i[2 * m + 2:], g=j[:ek] if ek else torch.zeros(1, dtype=torch.int32, device=dev),
                               d=j[ek:2 * ek] if ek else torch.zeros(1, dtype=torch.int32, device=dev), lo=0, hi=m))
         return views
+
+
+def exchange_streams(ss, send_ids, recv_ids, group=None):
+    """Move streams between the ranks' sets (rebalancing a stream-sharded
+    deployment to a ``balanced_assignment``, a swap, an eviction):
+    ``send_ids[p]`` lists the streams of ``ss`` that go to peer p and
+    ``recv_ids[p]`` the streams of ``ss`` that take the ones arriving from peer
+    p, in the order the peer listed them -- one list per rank of the group,
+    this rank's own included (``send_ids[rank]`` -> ``recv_ids[rank]`` is a
+    local copy).
+
+    ``pack_select`` per peer, one all-to-all of the sizes, ONE
+    ``all_to_all_single`` of the packed bytes (over gloo, device buffers are
+    staged through the host), ``unpack_select`` per peer.  Every pack happens
+    before any unpack, so a swap of two ranks' streams and a rank's own
+    loop-back are well defined.  A moved stream continues exactly as the
+    original would have (nothing is flushed).  Sent streams are NOT reset: the
+    caller ``reset_select``s them for a move instead of a copy.
+
+    A peer that sent another number of streams than ``recv_ids[p]`` lists, or a
+    stream listed twice on the receiving side, raises ``ValueError`` on this
+    rank after the collectives (so that no peer is left waiting in one) and
+    before anything of ``ss`` is changed."""
+    on = dist.is_available() and dist.is_initialized()
+    world = dist.get_world_size(group) if on else 1
+    if len(send_ids) != world or len(recv_ids) != world:
+        raise ValueError("send_ids and recv_ids need one list per rank (%d)" % world)
+    dev = ss.device
+    send = [ss._select_ids(x) for x in send_ids]
+    recv = [ss._select_ids(x) for x in recv_ids]
+    bufs = [ss.pack_select(i) for i in send]
+    in_sizes = [int(b.numel()) for b in bufs]
+    if world == 1:
+        counts, out_sizes, got = [send[0].numel()], in_sizes, bufs[0]
+    else:
+        meta = torch.tensor([[n, i.numel()] for n, i in zip(in_sizes, send)], dtype=torch.int64, device=dev).reshape(-1)
+        rmeta = torch.empty_like(meta)
+        _all_to_all_single(rmeta, meta, group=group)
+        rmeta = rmeta.reshape(world, 2).cpu()
+        out_sizes, counts = rmeta[:, 0].tolist(), rmeta[:, 1].tolist()
+        got = torch.empty(sum(out_sizes), dtype=torch.uint8, device=dev)
+        _all_to_all_single(got, torch.cat(bufs), out_sizes, in_sizes, group=group)
+    for p in range(world):
+        if counts[p] != recv[p].numel():
+            raise ValueError("peer %d sent %d stream(s), recv_ids[%d] lists %d" % (p, counts[p], p, recv[p].numel()))
+    everyone = torch.cat(recv).cpu()
+    if everyone.numel() != torch.unique(everyone).numel():
+        raise ValueError("a stream is listed more than once in recv_ids")
+    for p, part in enumerate(torch.split(got, out_sizes)):
+        ss.unpack_select(recv[p], part)
 
 
 def allgather_packed(ss, group=None):

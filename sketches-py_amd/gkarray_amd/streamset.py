@@ -702,6 +702,100 @@ class StreamSet:
             raise UnequalEpsilonException("Cannot merge two GKArrays with different epsilon values")
         self._check(rc)
 
+    # ---- stream transfer (gk_pack_select / gk_unpack_select) ----------------
+    def pack_select_bytes(self, ids):
+        """Size of ``pack_select(ids)``."""
+        i = self._select_ids(ids)
+        K = i.numel()
+        b = ctypes.c_int64(0)
+        with self._ctx():
+            self._check(self._lib.gk_pack_select_bytes(self._h, _ptr(i) if K else None, K, ctypes.byref(b),
+                                                       self._sp()))
+        self._inflight = None  # (the call synchronised)
+        return b.value
+
+    def pack_select(self, ids, buf=None):
+        """The complete state of the listed streams -- tables, pending values,
+        n / min / max / sum / avg, nothing flushed -- as one packed state of
+        ``len(ids)`` streams (``gk_pack_select``; layout in csrc/gk_pack.h),
+        row k for ``ids[k]``: a uint8 tensor on the set's device.  The set is
+        not changed.  Ids may repeat and come in any order.  ``buf``: a
+        contiguous uint8 tensor of at least ``pack_select_bytes(ids)`` bytes on
+        the set's device to write into."""
+        i = self._select_ids(ids)
+        K = i.numel()
+        if buf is None:
+            buf = torch.empty(self.pack_select_bytes(i), dtype=torch.uint8, device=self.device)
+        if buf.dtype != torch.uint8 or not buf.is_contiguous() or buf.device != self.device:
+            raise ValueError("buf must be a contiguous uint8 tensor on %s" % self.device)
+        with self._ctx():
+            self._check(self._lib.gk_pack_select(self._h, _ptr(i) if K else None, K, _ptr(buf), buf.numel(),
+                                                 self._sp()))
+        self._inflight = None
+        return buf
+
+    def unpack_select(self, ids, buf):
+        """``self[ids[k]] := stream k of buf`` (``gk_unpack_select``): the
+        complete state of each listed stream is replaced by the packed one, so
+        that it continues exactly as the packed stream would have.  ``buf`` is
+        a packed state of ``len(ids)`` streams (``pack_select`` / ``pack``; it
+        is moved to the set's device if it lives elsewhere).  Every refusal --
+        an id outside the set or listed twice, a stream count or eps that does
+        not match, a malformed buffer -- comes before anything is changed."""
+        i = self._select_ids(ids)
+        K = i.numel()
+        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.dim() != 1:
+            raise ValueError("buf must be a one-dimensional uint8 tensor")
+        if buf.device != self.device:
+            buf = buf.to(self.device)
+        buf = buf.contiguous()
+        if buf.numel() < 64:
+            raise ValueError("buf is shorter than a packed state's header")
+        with self._ctx():
+            rc = self._lib.gk_unpack_select(self._h, _ptr(i) if K else None, K, _ptr(buf), self._sp())
+        self._inflight = None
+        if rc == L.GK_E_EPS_MISMATCH:
+            from .gkarray import UnequalEpsilonException
+            raise UnequalEpsilonException(L.last_error(self._lib))
+        self._check(rc)
+
+    def take(self, ids, device=None):
+        """A new set of ``len(ids)`` streams and the same eps holding copies of
+        the listed streams (``pack_select`` + ``fold_packed``); this set is not
+        changed.  ``device``: where the new set lives -- this set's device by
+        default, another GPU, or ``"cpu"`` for the host engine."""
+        i = self._select_ids(ids)
+        buf = self.pack_select(i)
+        out = StreamSet(i.numel(), self.eps, device=self.device if device is None else device)
+        if buf.device != out.device:
+            buf = buf.to(out.device)
+        out.fold_packed([buf])
+        return out
+
+    def put(self, ids, other):
+        """``self[ids[k]] := other[k]`` for every k: ``other`` is a set of
+        ``len(ids)`` streams (either engine, any device) and is not changed
+        (``other.pack()`` + ``unpack_select``)."""
+        if not isinstance(other, StreamSet):
+            raise ValueError("other must be a StreamSet")
+        i = self._select_ids(ids)
+        if other.num_streams != i.numel():
+            raise ValueError("other holds %d streams, %d ids are listed" % (other.num_streams, i.numel()))
+        self.unpack_select(i, other.pack())
+
+    def resized(self, num_streams):
+        """A new set of ``num_streams`` streams on this set's device: streams
+        [0, min(S, num_streams)) are copies of this set's, the rest are empty;
+        this set is not changed.  How a keyed-ingest user grows a set."""
+        num_streams = int(num_streams)
+        if num_streams < 0:
+            raise ValueError("num_streams must be >= 0")
+        keep = torch.arange(min(self.num_streams, num_streams), dtype=torch.int32)
+        out = StreamSet(num_streams, self.eps, device=self.device)
+        if keep.numel():
+            out.unpack_select(keep, self.pack_select(keep))
+        return out
+
     def merge_compress(self, v=None, g=None, d=None, eoffs=None):
         """``merge_compress(entries)`` (gk:63-109) on every stream; stream s
         merges records [eoffs[s], eoffs[s+1]) (sorted by value).  With no
