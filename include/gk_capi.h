@@ -21,16 +21,7 @@
  *    re-run by the device itself.  Part of an ingest (the sequential
  *    _sum/_avg chains of streams longer than 16384 values) runs on a stream
  *    the set owns; `stream` is made to wait for it, so every later call
- *    enqueued on `stream` sees the finished state.  Optionally
- *    (GK_HOST_CHAINS=1 or GK_HOST_CHAIN_MIN in the environment; off by
- *    default) the chains of the few longest streams (>= 2^20 values) are
- *    walked on host cores by a worker thread of the set: the call only
- *    hands them over (it does not block)
- *    and `stream` waits for the worker on the device (a kernel polling a
- *    pinned flag, bounded at 20 s; a failed host walk is redone on the
- *    device, same bits).  The set's next call, gk_sync and gk_destroy first
- *    wait for that worker on the host.  While `stream` is being captured
- *    into a graph, no chain is handed to the host.  The caller keeps input
+ *    enqueued on `stream` sees the finished state.  The caller keeps input
  *    buffers alive and unchanged until the set's next call or gk_sync: a
  *    stream that needs a class whose arena has no free slot yet is deferred
  *    and re-run from them by the host runtime before the next call proceeds.
@@ -479,11 +470,6 @@ double gk_eps(const gk_set* set);
 int gk_flush_period(const gk_set* set);       /* int(1.0/eps) + 1 (gk:60)  */
 int gk_capacity(const gk_set* set, int cls);  /* table capacity of a class */
 int64_t gk_num_promoted(const gk_set* set);   /* streams in the large class */
-/* Streams whose gk:52-59 chains the host walked in the last completed
- * ingest (host-walked chains; 0 when none were picked or
- * the walk failed and the device walked them), -1 for a bad set.  Waits for
- * the set's host worker.  Diagnostics only: results never depend on it. */
-int64_t gk_host_chains_taken(gk_set* set);
 
 /* Kernel timing: `on` bit 0 -- gk_ingest records HIP events around the
  * flush kernel it launches on `stream`; bit 1 -- also around the call's

@@ -6,21 +6,13 @@
 // declared in include/gk_capi.h with the reference method it replaces.
 #include <hip/hip_runtime.h>
 
-#include <sched.h>
-
 #include <algorithm>
-#include <atomic>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <condition_variable>
-#include <deque>
 #include <functional>
-#include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "gk_capi.h"
@@ -29,7 +21,6 @@
 #include "gk_format.h"
 #include "gk_launch.h"
 #include "gk_state.h"
-#include "gk_host_stats.h"
 
 namespace {
 
@@ -171,33 +162,11 @@ struct gk_set {
   // the flush list (k_select_check)
   int32_t* d_sel = nullptr;
   int64_t sel_words = 0;
-  // Host-walked chains: the gk:52-59 chains of the
-  // longest streams run on host cores beside the GPU ingest.  hc_min: shortest
-  // stream taken (0: off; GK_HOST_CHAINS=0 / GK_HOST_CHAIN_MIN); hc_threads:
-  // host threads (GK_HOST_CHAIN_THREADS); at most 4 x hc_threads x the
-  // longest length values go to the host per call.
-  int64_t hc_min = 0;
-  int hc_rel = 75;  // ... and >= this % of the longest stream (GK_HOST_CHAIN_REL)
-  int hc_threads = 1;
-  GKHostChainRec* d_hc = nullptr;   // GK_HC_MAX records (device)
-  int32_t* d_hc_count = nullptr;
-  GKHostChainRec* h_hc = nullptr;   // pinned copies
-  int32_t* h_hc_count = nullptr;
-  hipEvent_t ev_hc = nullptr;       // the records' D2H copy
-  bool hc_active = false;           // this call enqueued k_hc_prep
-  const double* hc_x = nullptr;     // the call's values and offsets
-  const int64_t* hc_offs = nullptr;
   bool forked = false;              // stats_fork launched on aux; stats_join / stats_abort joins it
   bool sl_inline = false;           // no fork: stats_join launches k_stats_long on the call's stream
   const double* sl_x = nullptr;     // (its arguments)
   const int64_t* sl_offs = nullptr;
-  // one copy stream for every host thread's chunk copies, made at the first
-  // host-walked chain (the box runs 4 hardware queues per process: a copy
-  // stream sharing the ingest's or aux's queue waits behind their kernels --
-  // 16 per-thread streams gave 12 GB/s instead of ~55); per host thread two
-  // pinned chunk buffers and their events
-  hipStream_t hc_copy = nullptr;
-  // k_presort of the long streams' flush batches runs here beside the short
+  // the presort of the long streams' flush batches runs here beside the short
   // streams' chains (k_stats on the caller's stream); the ingest waits for it
   hipStream_t aux2 = nullptr;
   hipStream_t aux3 = nullptr;    // the presort when k_ingest_wg runs beside it (ps.done)
@@ -207,29 +176,6 @@ struct gk_set {
   hipEvent_t ev_go = nullptr;  // the call's counters zeroed: k_ingest_wg may be launched (GK_WG_EARLY)
   bool wg_early = false;       // this call's k_ingest_wg was launched by stats_fork, ahead of the chain walks
   bool wg_trace = false;       // GK_WG_TRACE=1 at creation: its stream count per completed call on stderr (tests)
-  std::vector<hipStream_t> hc_streams;
-  std::vector<double*> hc_buf;
-  std::vector<hipEvent_t> hc_ev;
-  // The host walk is asynchronous (round 4): gk_ingest* only hands the call
-  // to a worker thread of the set and enqueues the join on the caller's
-  // stream (k_hc_wait on a pinned flag the worker writes, then the records'
-  // copy, k_hc_apply, and k_hc_fallback which walks the picked chains on the
-  // device if the host walk failed).  The next call on the set (or gk_sync /
-  // gk_destroy) waits for the worker first, so the call's input buffers are
-  // read by the worker no longer than the header's contract allows.
-  std::thread hc_thr;
-  std::mutex hc_mu;
-  std::condition_variable hc_cv;
-  std::deque<uint64_t> hc_jobs;             // calls whose chains wait for the worker
-  bool hc_stop = false;
-  uint64_t hc_seq = 0;                      // sequence number of the last handed-out call
-  unsigned long long* h_hc_flag = nullptr;  // pinned, device-visible: (seq << 2) | 1 done / 2 failed
-  int32_t* d_hc_fail = nullptr;             // device: this call's walk failed (set by k_hc_wait)
-  int hc_fail_inject = 0;                   // GK_HC_FAIL=1 (tests): the worker reports a failure
-  double hc_timeout_s = 20.0;               // k_hc_wait's bound on the host walk
-  int64_t hc_last_taken = 0;                // streams the host walked in the last completed job
-  int hc_last_rc = GK_OK;
-  std::string hc_last_msg;
   // timing: event pairs recorded around the timed launches, summed at read
   bool timing = false;        // events around the class-0 ingest launch (gk_timing_enable bit 0)
   bool timing_stats = false;  // and around stats_fork's launches (bit 1: two more markers per call)
@@ -461,13 +407,10 @@ int replay_deferred(gk_set* h, hipStream_t s) {
   return fail(GK_E_OVERFLOW, "deferred streams could not be placed in a capacity class");
 }
 
-void hc_drain(gk_set* h);
-
 // Before a call (and in gk_sync): settle the previous call -- wait for it when
 // it may have deferred streams (some class could run out of slots), re-run
 // those, report its asynchronous errors.
 int settle(gk_set* h, hipStream_t s, bool block) {
-  hc_drain(h);  // the last call's host walk reads its inputs: done before anything else
   poll(h, block || h->last.may_defer);
   if (h->done_pending) return GK_OK;  // still running, and it cannot have deferred anything
   return replay_deferred(h, s);
@@ -583,199 +526,18 @@ hipError_t launch_class(gk_set* h, int c, const double* x, const int64_t* offs, 
 // only lists the long streams)
 bool stats_fused(const gk_set* h) { return h->fused_stats > 0 && h->st.cap[0] == GK_SMALL_CAP; }
 
-// doubles per pinned chunk copy (GK_HOST_CHAIN_CHUNK_MB, default 8 MiB)
-const int64_t kHcChunk = []() {
-  int64_t mb = 8;
-  if (const char* e = getenv("GK_HOST_CHAIN_CHUNK_MB")) mb = std::max<int64_t>(1, std::min<int64_t>(256, atoll(e)));
-  return mb << 17;
-}();
-
-// Per-thread copy stream, chunk buffers and events for the first `t` host
-// threads (made on first use, kept until gk_destroy).
-int hc_ensure(gk_set* h, int t) {
-  while ((int)h->hc_streams.size() < t) {
-    h->hc_streams.push_back(h->hc_copy);
-    for (int b = 0; b < 2; ++b) {
-      double* p = nullptr;
-      if (hipHostMalloc(&p, kHcChunk * sizeof(double)) != hipSuccess) return fail(GK_E_NOMEM, "host-chain buffer");
-      h->hc_buf.push_back(p);
-      hipEvent_t e = nullptr;
-      HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      h->hc_ev.push_back(e);
-    }
-  }
-  return GK_OK;
-}
-
-// Walk the chains k_hc_prep picked (blocking): the longest streams first,
-// each on one host thread, its values streamed device -> pinned host in
-// 2 MiB chunks (the next chunk's copy in flight while the chain walks this
-// one) and fed to the host engine's gk:52-59 step.  The final state goes
-// back into the pinned records (applied on the device by stats_join).
-int run_host_chains(gk_set* h, int* taken) {
-  *taken = 0;
-  HIP_TRY(hipEventSynchronize(h->ev_hc));
-  const int K = std::min(*h->h_hc_count, GK_HC_MAX);
-  if (K <= 0) return GK_OK;
-  if (!h->hc_copy) HIP_TRY(hipStreamCreateWithFlags(&h->hc_copy, hipStreamNonBlocking));
-  // the picked records (k_hc_prep, complete: ev_hc followed it)
-  HIP_TRY(hipMemcpyAsync(h->h_hc, h->d_hc, K * sizeof(GKHostChainRec), hipMemcpyDeviceToHost, h->hc_copy));
-  HIP_TRY(hipStreamSynchronize(h->hc_copy));
-  const int T = std::max(1, std::min(h->hc_threads, K));
-  int rc = hc_ensure(h, T);
-  if (rc) return rc;
-  std::atomic<int> next{0};
-  std::atomic<int> err{0};
-  std::vector<std::string> msg(T);
-  std::vector<double> t_walk(T, 0.0), t_wait(T, 0.0);
-  std::vector<int64_t> v_done(T, 0);
-  using clk = std::chrono::steady_clock;
-  const auto t_start = clk::now();
-  auto sec = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
-  auto worker = [&](int t) {
-    hipStream_t hs = h->hc_streams[t];
-    double* buf[2] = {h->hc_buf[2 * t], h->hc_buf[2 * t + 1]};
-    hipEvent_t ev[2] = {h->hc_ev[2 * t], h->hc_ev[2 * t + 1]};
-    for (;;) {
-      const int k = next.fetch_add(1);
-      if (k >= K || err.load()) return;
-      GKHostChainRec& r = h->h_hc[k];
-      GKHostStats hs_state{r.n, r.sum, r.avg, r.mn, r.mx};
-      const double* src = h->hc_x + r.xo;
-      auto issue = [&](int64_t off, int b) -> bool {
-        const int64_t c = std::min(kHcChunk, r.len - off);
-        return hipMemcpyAsync(buf[b], src + off, c * sizeof(double), hipMemcpyDefault, hs) == hipSuccess &&
-               hipEventRecord(ev[b], hs) == hipSuccess;
-      };
-      bool ok = r.len <= 0 || issue(0, 0);
-      int cur = 0;
-      for (int64_t off = 0; ok && off < r.len;) {
-        const int64_t c = std::min(kHcChunk, r.len - off);
-        if (off + c < r.len) ok = issue(off + c, cur ^ 1);
-        const auto a = clk::now();
-        ok = ok && hipEventSynchronize(ev[cur]) == hipSuccess;
-        if (!ok) break;
-        const auto b = clk::now();
-        gk_host_stat_run(hs_state, buf[cur], c);
-        t_wait[t] += sec(a, b);
-        t_walk[t] += sec(b, clk::now());
-        v_done[t] += c;
-        off += c;
-        cur ^= 1;
-      }
-      if (!ok) {
-        msg[t] = hipGetErrorString(hipGetLastError());
-        err.store(1);
-        (void)hipStreamSynchronize(hs);
-        return;
-      }
-      r.sum = hs_state.sum;
-      r.avg = hs_state.avg;
-      r.mn = hs_state.mn;
-      r.mx = hs_state.mx;
-    }
-  };
-  std::vector<std::thread> pool;
-  pool.reserve(T - 1);
-  for (int t = 1; t < T; ++t) pool.emplace_back(worker, t);
-  worker(0);
-  for (auto& th : pool) th.join();
-  static const bool hc_trace = getenv("GK_HC_TRACE") != nullptr;
-  if (hc_trace) {
-    double w = 0, q = 0;
-    int64_t v = 0;
-    for (int t = 0; t < T; ++t) {
-      w += t_walk[t];
-      q += t_wait[t];
-      v += v_done[t];
-    }
-    fprintf(stderr, "[gk] host chains: %d streams, %lld values on %d threads in %.1f ms (walk %.1f ms = %.2f ns/value, "
-            "copy waits %.1f ms, summed over threads)\n", K, (long long)v, T, 1e3 * sec(t_start, clk::now()), 1e3 * w,
-            v ? 1e9 * w / (double)v : 0.0, 1e3 * q);
-  }
-  if (err.load()) {
-    for (const std::string& m : msg)
-      if (!m.empty()) return fail(GK_E_HIP, "host-walked chains: chunk copy failed: %s", m.c_str());
-    return fail(GK_E_HIP, "host-walked chains: chunk copy failed");
-  }
-  *taken = K;
-  return GK_OK;
-}
-
-// The set's host-walk worker: walks the chains of each handed-out call (in
-// order), then publishes (seq << 2) | status in the pinned flag that the
-// call's k_hc_wait reads -- always, on failure too (status 2: k_hc_fallback
-// then walks those streams on the device).
-void hc_worker_main(gk_set* h) {
-  (void)hipSetDevice(h->device);
-  for (;;) {
-    uint64_t seq = 0;
-    {
-      std::unique_lock<std::mutex> lk(h->hc_mu);
-      h->hc_cv.wait(lk, [h] { return h->hc_stop || !h->hc_jobs.empty(); });
-      if (h->hc_jobs.empty()) return;  // stop, nothing left
-      seq = h->hc_jobs.front();
-    }
-    int taken = 0;
-    int rc = run_host_chains(h, &taken);
-    std::string msg = rc ? g_err : std::string();
-    if (!rc && h->hc_fail_inject) {
-      rc = GK_E_HIP;
-      taken = 0;
-      msg = "host-walked chains: failure injected (GK_HC_FAIL)";
-    }
-    __atomic_store_n(h->h_hc_flag, (unsigned long long)((seq << 2) | (rc == GK_OK ? 1u : 2u)), __ATOMIC_RELEASE);
-    {
-      std::lock_guard<std::mutex> lk(h->hc_mu);
-      h->hc_jobs.pop_front();
-      h->hc_last_taken = taken;
-      h->hc_last_rc = rc;
-      h->hc_last_msg = msg;
-    }
-    h->hc_cv.notify_all();
-  }
-}
-
-// Wait until the worker has walked every handed-out call (start of the next
-// call, gk_sync, gk_destroy).  A failed walk is not an error of the set: the
-// device walked those chains instead (k_hc_fallback).
-void hc_drain(gk_set* h) {
-  if (!h->hc_thr.joinable()) return;
-  std::unique_lock<std::mutex> lk(h->hc_mu);
-  h->hc_cv.wait(lk, [h] { return h->hc_jobs.empty(); });
-}
-
-void hc_shutdown(gk_set* h) {
-  if (!h->hc_thr.joinable()) return;
-  {
-    std::lock_guard<std::mutex> lk(h->hc_mu);
-    h->hc_stop = true;
-  }
-  h->hc_cv.notify_all();
-  h->hc_thr.join();
-}
-
 // A call that fails between stats_fork and stats_join: best effort, `s` still
-// waits for the aux work, and chains the host would have walked are walked on
-// the device (k_hc_fallback with the fail word set).
+// waits for the aux work.
 void stats_abort(gk_set* h, hipStream_t s) {
   if (h->wg_early) (void)hipStreamWaitEvent(s, h->ev_wg, 0);  // (launched by stats_fork: joined here too)
   h->wg_early = false;
   if (h->forked) (void)hipStreamWaitEvent(s, h->ev_join, 0);
   if (h->sl_inline)
-    (void)gk_launch_stats_long(h->st, h->sl_x, h->sl_offs, h->d_long_list, nullptr, h->d_long_count, nullptr, s);
+    (void)gk_launch_stats_long(h->st, h->sl_x, h->sl_offs, h->d_long_list, nullptr, h->d_long_count, s);
   h->sl_inline = false;
   if (h->presort_active) (void)hipStreamWaitEvent(s, h->ev_presort, 0);
   h->presort_active = false;
-  if (h->hc_active) {
-    const int32_t one = 1;
-    if (hipMemcpyAsync(h->d_hc_fail, &one, sizeof(one), hipMemcpyHostToDevice, s) == hipSuccess)
-      (void)gk_launch_hc_fallback(h->st, h->hc_x, h->hc_offs, h->d_long_list, h->d_long_n, h->d_hc_count,
-                                  h->d_hc_fail, s);
-    (void)hipStreamSynchronize(s);  // (`one` lives on this stack frame)
-  }
   h->forked = false;
-  h->hc_active = false;
 }
 
 int stats_fork(gk_set* h, const double* x, const int64_t* offs, hipStream_t s, int force) {
@@ -806,14 +568,14 @@ int stats_fork(gk_set* h, const double* x, const int64_t* offs, hipStream_t s, i
   HIP_TRY(gk_launch_stats(h->st, offs, h->d_long_list, h->d_long_count, s));
   // k_long_prep sorts the list (longest first) and plans the presort /
   // workgroups -- unless the small-class launch carries the stats role
-  // (P <= 128: no presort, no workgroups) and no host chain is picked from
-  // the sorted list: then it is not needed at all (k_stats_long reads the
-  // list in k_lengths' order and the pre-call n from k_lengths' snapshot).
+  // (P <= 128: no presort, no workgroups): then it is not needed at all
+  // (k_stats_long reads the list in k_lengths' order and the pre-call n from
+  // k_lengths' snapshot).
   // k_stats_long must be the first work on `aux` after the fork: queued behind
   // anything, its waves reach the CUs after the persistent ingest grid and run
   // ~3x longer beside it (round 5's k_long_prep on aux: cfg4 x 8 shards
   // 84 -> 118 ms per step, profiles/r05/r05E_*)
-  const bool prep = !(stats_fused(h) && !(h->hc_min > 0));
+  const bool prep = !stats_fused(h);
   if (prep)
     HIP_TRY(gk_launch_long_prep(h->st, offs, h->d_long_list, h->d_long_n, h->d_long_count, h->ps, s,
                                 early ? h->d_ctr + GK_CTR_WGGO : nullptr));
@@ -827,30 +589,6 @@ int stats_fork(gk_set* h, const double* x, const int64_t* offs, hipStream_t s, i
     HIP_TRY(hipEventRecord(h->ev_wg, h->aux2));
     h->wg_early = true;
   }
-  // the longest chains to host cores: k_hc_prep picks them (k_stats_long
-  // skips them) ahead of the fork, so that `aux` holds nothing but
-  // k_stats_long and its waves reach the CUs before the ingest grid of this
-  // call (queued behind the pick and its copies they lost that race and ran
-  // ~3x longer beside the ingest: cfg4 x8 shards 82 -> 110 ms per step).  The
-  // records go to the host on the copy stream; the host walks the chains in
-  // stats_join, while the GPU ingests.
-  h->hc_active = false;
-  // (not while `s` is being captured into a graph: a replay would not hand
-  // the call to the worker; the device walks every chain then)
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (h->hc_min > 0 && s && hipStreamIsCapturing(s, &cap) != hipSuccess) cap = hipStreamCaptureStatusNone;
-  const bool hc_on = h->hc_min > 0 && cap == hipStreamCaptureStatusNone;
-  if (hc_on) {
-    // (only the pick's count comes back here; the records follow in
-    // run_host_chains when there are any -- every stream of the process
-    // shares 4 hardware queues, and copies queued beside `aux` delayed it)
-    HIP_TRY(gk_launch_hc_prep(h->st, offs, h->d_long_list, h->d_long_n, h->d_long_count, h->hc_min, h->hc_rel,
-                              4 * (int64_t)h->hc_threads, h->d_hc, h->d_hc_count, s));
-    HIP_TRY(hipMemcpyAsync(h->h_hc_count, h->d_hc_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipEventRecord(h->ev_hc, s));
-    h->hc_x = x;
-    h->hc_offs = offs;
-  }
   const bool presort = h->ps.list_ws && h->ps.ws && h->ps.ws_cap > 0;
   // No fork when nothing but k_stats_long would go to the aux streams and the
   // set's last ingest call listed no long stream (its count comes back with
@@ -860,7 +598,7 @@ int stats_fork(gk_set* h, const double* x, const int64_t* offs, hipStream_t s, i
   // on the step's critical path, and a k_stats_long dispatched beside the
   // ingest grid cost the cfg3 launch 8 % (profiles/r06/r06q_*).  A wrong
   // guess costs time only: the walk is the same on either stream.
-  h->sl_inline = stats_fused(h) && !prep && !early && !hc_on && !presort && !h->aux2 && h->h_ctr &&
+  h->sl_inline = stats_fused(h) && !prep && !early && !presort && !h->aux2 && h->h_ctr &&
                  h->h_ctr[GK_CTR_LONG] == 0 && !getenv("GK_SL_FORK");
   if (h->sl_inline) {
     h->sl_x = x;
@@ -890,8 +628,7 @@ int stats_fork(gk_set* h, const double* x, const int64_t* offs, hipStream_t s, i
     h->forked = true;
     if (sl_order) HIP_TRY(hipEventRecord(h->ev_slgo, h->aux));
     HIP_TRY(gk_launch_stats_long(h->st, x, offs, h->d_long_list, prep ? h->d_long_n : nullptr, h->d_long_count,
-                                 hc_on ? h->d_hc_count : nullptr, h->aux));
-    h->hc_active = hc_on;  // (stats_join hands the picked chains to the worker)
+                                 h->aux));
     HIP_TRY(hipEventRecord(h->ev_join, h->aux));
   }
   if (sl_order) HIP_TRY(hipStreamWaitEvent(s, h->ev_slgo, 0));
@@ -922,7 +659,7 @@ int stats_join(gk_set* h, hipStream_t s, const GKQuery& q) {
   }
   if (h->sl_inline) {
     h->sl_inline = false;
-    HIP_TRY(gk_launch_stats_long(h->st, h->sl_x, h->sl_offs, h->d_long_list, nullptr, h->d_long_count, nullptr, s));
+    HIP_TRY(gk_launch_stats_long(h->st, h->sl_x, h->sl_offs, h->d_long_list, nullptr, h->d_long_count, s));
   } else {
     HIP_TRY(hipStreamWaitEvent(s, h->ev_join, 0));
   }
@@ -930,33 +667,6 @@ int stats_join(gk_set* h, hipStream_t s, const GKQuery& q) {
   if (h->presort_active) {
     h->presort_active = false;
     HIP_TRY(hipStreamWaitEvent(s, h->ev_presort, 0));
-  }
-  if (h->hc_active) {
-    h->hc_active = false;
-    // hand the call to the worker (it walks while the GPU ingests) and join
-    // it on `s`: nothing here waits on the host
-    if (!h->hc_thr.joinable()) {
-      h->hc_stop = false;
-      try {
-        h->hc_thr = std::thread(hc_worker_main, h);
-      } catch (...) {
-        return fail(GK_E_HIP, "cannot start the host-chain worker thread");
-      }
-    }
-    const uint64_t seq = ++h->hc_seq;
-    {
-      std::lock_guard<std::mutex> lk(h->hc_mu);
-      h->hc_jobs.push_back(seq);
-    }
-    h->hc_cv.notify_all();
-    HIP_TRY(gk_launch_hc_wait(h->h_hc_flag, seq, h->d_hc_fail, h->hc_timeout_s, s));
-    // (the copy engine reads the pinned records once k_hc_wait has seen the
-    // worker's flag; the next call's readback of them is ordered after it:
-    // its fork waits on `s`, and the next call first drains the worker)
-    HIP_TRY(hipMemcpyAsync(h->d_hc, h->h_hc, GK_HC_MAX * sizeof(GKHostChainRec), hipMemcpyHostToDevice, s));
-    HIP_TRY(gk_launch_hc_apply(h->st, h->d_hc, h->d_hc_count, h->d_hc_fail, s));
-    HIP_TRY(gk_launch_hc_fallback(h->st, h->hc_x, h->hc_offs, h->d_long_list, h->d_long_n, h->d_hc_count,
-                                  h->d_hc_fail, s));
   }
   // (+ the _min/_max markers of the small-class launch's answers when it
   // carried the stats role: its chains are final here)
@@ -1240,30 +950,6 @@ int gk_create(int64_t num_streams, double eps, int64_t cap_hint, int device, gk_
   h->device = device;
   h->vpl = h->P <= 1024 ? vpl_for(h->P) : 0;  // (registers of the capacity-class kernels)
   if (const char* fs = getenv("GK_FUSED_STATS")) h->fused_stats = std::max(0, std::min(64, atoi(fs)));
-  // host-walked chains: off by default since round 4 (the device's
-  // speculative walk of k_stats_long runs a 10^7-value chain in a few ms,
-  // faster than a host core plus the PCIe copy of its values).  GK_HOST_CHAINS=1
-  // turns them on for streams of >= 2^20 values (GK_HOST_CHAIN_MIN sets the
-  // length and turns them on too; GK_HOST_CHAINS=0 wins) on up to 16 host
-  // threads (GK_HOST_CHAIN_THREADS; the process's CPU share: its affinity
-  // set, OMP_NUM_THREADS if lower)
-  h->hc_min = 0;
-  if (const char* e = getenv("GK_HOST_CHAINS"))
-    if (atoi(e) != 0) h->hc_min = (int64_t)1 << 20;
-  if (const char* e = getenv("GK_HOST_CHAIN_MIN")) h->hc_min = std::max<int64_t>(0, atoll(e));
-  if (const char* e = getenv("GK_HOST_CHAINS"))
-    if (atoi(e) == 0) h->hc_min = 0;
-  if (const char* e = getenv("GK_HOST_CHAIN_REL")) h->hc_rel = std::max(0, std::min(100, atoi(e)));
-  {
-    int t = 16;
-    cpu_set_t cs;
-    if (sched_getaffinity(0, sizeof(cs), &cs) == 0 && CPU_COUNT(&cs) > 0) t = std::min(t, CPU_COUNT(&cs));
-    if (const char* e = getenv("OMP_NUM_THREADS"))
-      if (atoi(e) > 0) t = std::min(t, atoi(e));
-    if (const char* e = getenv("GK_HOST_CHAIN_THREADS"))
-      if (atoi(e) > 0) t = atoi(e);
-    h->hc_threads = std::max(1, std::min(t, GK_HC_MAX));
-  }
   GKState& st = h->st;
   st.S = num_streams;
   st.eps = eps;
@@ -1345,10 +1031,6 @@ int gk_create(int64_t num_streams, double eps, int64_t cap_hint, int device, gk_
   okm &= hipMalloc(&h->d_long_n, S * sizeof(int64_t)) == hipSuccess;
 
   okm &= hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking) == hipSuccess;
-  // (hc_copy is made on first use, run_host_chains: an idle stream still
-  // takes a slot in the round-robin over the box's 4 hardware queues, and
-  // with 8 sets the long chains' `aux` then shared the caller's queue more
-  // often)
   // (aux2 only where the presort runs: every stream of a process shares the
   // box's 4 hardware queues, and a set's idle stream still takes a slot in
   // their round-robin -- with 8 sets of 3 streams the cfg4 shards' long
@@ -1358,18 +1040,6 @@ int gk_create(int64_t num_streams, double eps, int64_t cap_hint, int device, gk_
   okm &= hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) == hipSuccess;
   okm &= hipEventCreateWithFlags(&h->ev_slgo, hipEventDisableTiming) == hipSuccess;
   okm &= hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) == hipSuccess;
-  okm &= hipMalloc(&h->d_hc, GK_HC_MAX * sizeof(GKHostChainRec)) == hipSuccess;
-  okm &= hipMalloc(&h->d_hc_count, sizeof(int32_t)) == hipSuccess;
-  okm &= hipHostMalloc(&h->h_hc, GK_HC_MAX * sizeof(GKHostChainRec)) == hipSuccess;
-  okm &= hipHostMalloc(&h->h_hc_count, sizeof(int32_t)) == hipSuccess;
-  // the worker's flag: coherent pinned memory that k_hc_wait polls
-  okm &= hipHostMalloc(&h->h_hc_flag, sizeof(unsigned long long), hipHostMallocCoherent | hipHostMallocMapped) ==
-         hipSuccess;
-  okm &= hipMalloc(&h->d_hc_fail, sizeof(int32_t)) == hipSuccess;
-  okm &= h->d_hc_fail && hipMemset(h->d_hc_fail, 0, sizeof(int32_t)) == hipSuccess;
-  if (h->h_hc_flag) *h->h_hc_flag = 0;
-  if (const char* e = getenv("GK_HC_FAIL")) h->hc_fail_inject = atoi(e) != 0;
-  okm &= hipEventCreateWithFlags(&h->ev_hc, hipEventDisableTiming) == hipSuccess;
   if (h->P > 128 && !h->big[0]) {  // class 0 is a capacity-class kernel: presort long streams' batches
     okm &= hipMalloc(&h->ps.list_ws, S * sizeof(int64_t)) == hipSuccess;
     okm &= hipMalloc(&h->ps.list_b0, (S + 1) * sizeof(int64_t)) == hipSuccess;
@@ -1423,7 +1093,6 @@ int gk_create(int64_t num_streams, double eps, int64_t cap_hint, int device, gk_
 
 int gk_destroy(gk_set* h) {
   if (!h) return GK_OK;
-  hc_shutdown(h);  // the worker finishes its handed-out walks (their joins may be waiting on the device)
   (void)hipDeviceSynchronize();  // launches of this set may still be running on the caller's stream
   if (h->fold_scratch) gk_destroy(h->fold_scratch);
   if (h->self_scratch) gk_destroy(h->self_scratch);
@@ -1432,7 +1101,7 @@ int gk_destroy(gk_set* h) {
                   st.avg,     st.cls,        st.slot,        st.pbuf,        h->d_qs,
                   h->d_ctr,   h->d_zero_offs, h->d_long_list, h->d_long_n,
                   h->ps.list_ws, h->ps.list_b0, h->ps.ws,    h->ps.ws_need,  st.rtab,        st.n0,
-                  h->d_defer, h->d_hc,       h->d_hc_count,  h->d_hc_fail,   h->d_roll_prog,
+                  h->d_defer, h->d_roll_prog,
                   h->kg.ids[0], h->kg.ids[1], h->kg.vals[0], h->kg.vals[1],  h->kg.hist,     h->kg.sums,
                   h->kg.call, h->kg_vals,    h->kg_offs,     h->d_sel};
   for (void* p : ptrs)
@@ -1444,19 +1113,15 @@ int gk_destroy(gk_set* h) {
     if (h->d_ovfl[r]) (void)hipFree(h->d_ovfl[r]);
   for (auto* v : {&h->tev_flush, &h->tev_stats})
     for (hipEvent_t e : *v) (void)hipEventDestroy(e);
-  for (hipEvent_t e : {h->ev_fork, h->ev_join, h->ev_slgo, h->ev_done, h->ev_qs, h->ev_hc})
+  for (hipEvent_t e : {h->ev_fork, h->ev_join, h->ev_slgo, h->ev_done, h->ev_qs})
     if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : h->hc_ev) (void)hipEventDestroy(e);
-  if (h->hc_copy) (void)hipStreamDestroy(h->hc_copy);
   if (h->aux2) (void)hipStreamDestroy(h->aux2);
   if (h->aux3) (void)hipStreamDestroy(h->aux3);
   if (h->ev_presort) (void)hipEventDestroy(h->ev_presort);
   if (h->ev_wg) (void)hipEventDestroy(h->ev_wg);
   if (h->ev_go) (void)hipEventDestroy(h->ev_go);
-  for (double* p : h->hc_buf) (void)hipHostFree(p);
   if (h->aux) (void)hipStreamDestroy(h->aux);
-  for (void* p : {(void*)h->h_ws_need, (void*)h->h_ovf, (void*)h->h_ctr, (void*)h->h_qs, (void*)h->h_hc,
-                  (void*)h->h_hc_count, (void*)h->h_hc_flag, (void*)h->h_kg})
+  for (void* p : {(void*)h->h_ws_need, (void*)h->h_ovf, (void*)h->h_ctr, (void*)h->h_qs, (void*)h->h_kg})
     if (p) (void)hipHostFree(p);
   delete h;
   return GK_OK;
@@ -1472,7 +1137,6 @@ int gk_reset(gk_set* h, void* stream) {
   // critical path: ~90 us of idle GPU per step, 10 % of a 125k-stream rank
   // share.)  The last call's counters are consumed when they arrive: its
   // sticky errors are still reported, its deferred list is dropped.
-  hc_drain(h);  // (the host walk reads the last call's inputs)
   poll(h, false);
   if (h->done_pending) h->void_defer = true;
   else h->h_ctr[GK_CTR_DEFER] = 0;
@@ -2519,25 +2183,6 @@ double gk_eps(const gk_set* h) { return h ? h->eps : 0.0; }
 int gk_flush_period(const gk_set* h) { return h ? h->P : -1; }
 int gk_capacity(const gk_set* h, int cls) {
   return (h && cls >= 0 && cls < h->st.nclass) ? h->st.cap[cls] : -1;
-}
-int64_t gk_host_chains_taken(gk_set* h) {
-  if (!h) return -1;
-  hc_drain(h);
-  // the device's verdict on the last host-walked call: k_hc_wait sets the
-  // fail word when the worker reported a failure or its flag came too late
-  // (the chains were then walked on the device: k_hc_fallback), even if the
-  // worker finished OK afterwards
-  // (on the set's device, after the set's last call: ev_done follows its
-  // k_hc_wait; nothing else on the device is waited for -- ADVICE r05)
-  int32_t dev_fail = 0;
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  bool ok = hipSetDevice(h->device) == hipSuccess && hipEventSynchronize(h->ev_done) == hipSuccess &&
-            hipMemcpy(&dev_fail, h->d_hc_fail, sizeof(dev_fail), hipMemcpyDeviceToHost) == hipSuccess;
-  (void)hipSetDevice(prev);
-  if (!ok) return -1;
-  std::lock_guard<std::mutex> lk(h->hc_mu);
-  return (h->hc_last_rc == GK_OK && dev_fail == 0) ? h->hc_last_taken : 0;
 }
 
 int64_t gk_num_promoted(const gk_set* h) {

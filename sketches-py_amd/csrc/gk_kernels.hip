@@ -339,7 +339,7 @@ __device__ __forceinline__ GKRec* gk_table_ptr_cs(const GKState& st, int64_t s, 
 
 // Streams up to GK_STATS_LONG values have their gk:52-59 chains walked by the
 // stats role of the small-class launch (P <= 128) or by k_stats_short;
-// longer ones by k_stats_long (or on host cores), beside the ingest.
+// longer ones by k_stats_long, beside the ingest.
 #ifndef GK_STATS_LONG
 #define GK_STATS_LONG 16384  // longer streams go to k_stats_long (64 per wave, on a second HIP stream)
 #endif
@@ -442,11 +442,11 @@ __global__ __launch_bounds__(1024) void k_long_prep(GKState st, const int64_t* _
   for (int i = t; i < cnt; i += 1024) list_n[i] = st.n0[list[i]];
   if (!list_ws) return;
   __syncthreads();
-  // Presort plan (k_presort): every automatic flush of a listed class-0
+  // Presort plan (k_presort_reg): every automatic flush of a listed class-0
   // stream in this call gets a slot of P doubles in the workspace; list_ws[i]
   // = first slot offset (in doubles) or -1 (not presorted: the workspace is
   // too small -- the host grows it from *ws_need after the call), list_b0[i]
-  // = the stream's first global batch index (for k_presort's block mapping).
+  // = the stream's first global batch index (for k_presort_reg's wave mapping).
   // Only streams within a factor GK_PRESORT_REL of the longest one's flush
   // count are presorted: they alone can be the call's critical path (an
   // unsorted flush costs ~2-3x a presorted one), and sorting every listed
@@ -502,7 +502,7 @@ __global__ __launch_bounds__(1024) void k_long_prep(GKState st, const int64_t* _
       acc += v;
     }
     *ws_need = acc * st.P;
-    list_b0[cnt] = acc;  // total batches (k_presort's grid bound)
+    list_b0[cnt] = acc;  // total batches (k_presort_reg's grid bound)
   }
   __syncthreads();
   int64_t b = part[t];
@@ -524,196 +524,10 @@ __global__ __launch_bounds__(1024) void k_long_prep(GKState st, const int64_t* _
   }
 }
 
-// ===========================================================================
-// k_presort: the batch of every automatic flush of a listed long stream
-// (list_ws >= 0), sorted by (value, insertion index) -- Python's stable
-// sorted() of gk:71-72 -- into its workspace slot, ahead of k_ingest, so that
-// the flush (sequential per stream, on the critical path of long streams)
-// skips its in-gap ranking.  Batch 0 is the pre-call pending values followed
-// by the first `need` values; batch b > 0 is the next P values.  One
-// 256-thread block per batch (global batch id -> stream by binary search over
-// list_b0), bitonic sort of up to 1024 keys in LDS.
-// ===========================================================================
-__global__ __launch_bounds__(256) void k_presort(GKState st, const double* __restrict__ x,
-                                                 const int64_t* __restrict__ offs,
-                                                 const int32_t* __restrict__ list, const int32_t* __restrict__ count,
-                                                 const int64_t* __restrict__ list_n,
-                                                 const int64_t* __restrict__ list_ws,
-                                                 const int64_t* __restrict__ list_b0, double* __restrict__ ws) {
-  __shared__ double kv[1024];
-  __shared__ uint32_t ki[1024];
-  const int cnt = *count;
-  if (cnt <= 0) return;
-  const int64_t total = list_b0[cnt];
-  const int t = threadIdx.x;
-  const int P = st.P;
-  // a contiguous range of global batches per block: one binary search for
-  // its first stream slot, then the slot advances along the (ascending)
-  // list_b0 -- a search per batch was ~10 dependent global loads
-  const int64_t g0 = total * blockIdx.x / gridDim.x, g1 = total * (blockIdx.x + 1) / gridDim.x;
-  if (g0 >= g1) return;
-  int i = 0;
-  {
-    int lo = 0, hi = cnt - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (list_b0[mid] <= g0) lo = mid;
-      else hi = mid - 1;
-    }
-    i = lo;
-  }
-  int64_t bnext = i + 1 < cnt ? list_b0[i + 1] : INT64_MAX;  // first global batch of slot i + 1
-  int ci = -1;  // the slot whose parameters are loaded
-  int64_t wso = -1, b0 = 0, s = 0, xo = 0, need = 0;
-  int p = 0;
-  for (int64_t gb = g0; gb < g1; ++gb) {
-    while (gb >= bnext) {  // (slots without batches are passed over)
-      ++i;
-      bnext = i + 1 < cnt ? list_b0[i + 1] : INT64_MAX;
-    }
-    if (i != ci) {
-      ci = i;
-      wso = list_ws[i];
-      b0 = list_b0[i];
-      s = list[i];
-      xo = offs[s];
-      p = st.pend[s];
-      need = P - (list_n[i] % P);
-    }
-    if (wso < 0) continue;  // block-uniform
-    const int64_t b = gb - b0;
-    const double* pb = st.pbuf + s * (int64_t)st.pmax;
-    const int m = b == 0 ? p + (int)need : P;
-    const int64_t xb = b == 0 ? xo : xo + need + (b - 1) * P;  // first x value of the batch (after pending)
-    int N = 64;
-    while (N < m) N <<= 1;
-    for (int k = t; k < N; k += 256) {
-      double v = __longlong_as_double(0x7ff0000000000000LL);
-      if (k < m) v = (b == 0 && k < p) ? pb[k] : x[xb + (b == 0 ? k - p : k)];
-      kv[k] = v;
-      ki[k] = k < m ? (uint32_t)k : 0xffffffffu;
-    }
-    __syncthreads();
-    for (int k = 2; k <= N; k <<= 1) {
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int pp = t; pp < N / 2; pp += 256) {
-          const int a = ((pp & ~(j - 1)) << 1) | (pp & (j - 1));
-          const int c = a + j;
-          const double va = kv[a], vc = kv[c];
-          const uint32_t ia = ki[a], ic = ki[c];
-          const bool a_gt = (va > vc) || (!(va < vc) && ia > ic);
-          if (a_gt == ((a & k) == 0)) {
-            kv[a] = vc;
-            kv[c] = va;
-            ki[a] = ic;
-            ki[c] = ia;
-          }
-        }
-        __syncthreads();
-      }
-    }
-    double* out = ws + wso + b * P;
-    for (int k = t; k < m; k += 256) out[k] = kv[k];
-    __syncthreads();
-  }
-}
-
-// streams walked one wave each by k_stats_long (more: 64 per wave); also the
-// host-walked chains' limit
+// streams walked one wave each by k_stats_long (more: 64 per wave)
 #ifndef GK_SL_BCAST
 #define GK_SL_BCAST 1024
 #endif
-
-// ===========================================================================
-// Host-walked chains.  The gk:54 `_avg` update is three dependent float64
-// roundings per value: ~37 cycles per value on one gfx950 lane (15.7 ns), so
-// a 10^7-value stream is a 157 ms chain however the batch is spread.  A host
-// core runs the same three roundings at ~3 cycles each, so the longest
-// streams' chains go to host cores (gk_capi.cpp, over pinned chunk copies)
-// while the GPU ingests; k_hc_prep picks them and snapshots their pre-call
-// state, k_hc_apply writes the host's results back.
-// ===========================================================================
-__global__ __launch_bounds__(256) void k_hc_prep(GKState st, const int64_t* __restrict__ offs,
-                                                 const int32_t* __restrict__ list,
-                                                 const int64_t* __restrict__ list_n,
-                                                 const int32_t* __restrict__ count, int64_t min_len, int rel_pct,
-                                                 int64_t budget_factor, GKHostChainRec* __restrict__ recs,
-                                                 int32_t* __restrict__ hc_count) {
-  __shared__ int64_t pre[GK_HC_MAX];
-  __shared__ int64_t lmax;
-  const int t = threadIdx.x;
-  const int cnt = *count;
-  // (the list is sorted longest first: k_long_prep sorts up to
-  // GK_SORT_LONG_MAX >= GK_SL_BCAST entries, so eligibility is a prefix)
-  const bool on = min_len > 0 && cnt > 0 && cnt <= GK_SL_BCAST;
-  if (t == 0) lmax = on ? offs[(int64_t)list[0] + 1] - offs[list[0]] : 0;
-  __syncthreads();
-  // a chain shorter than rel_pct % of the longest finishes on the device
-  // under the longest stream's flushes anyway
-  const int64_t need = max(min_len, (int64_t)((double)lmax * (double)rel_pct / 100.0));
-  int64_t s = 0, xo = 0, L = 0;
-  if (on && t < cnt) {
-    s = list[t];
-    xo = offs[s];
-    L = offs[s + 1] - xo;
-  }
-  pre[t] = (on && t < cnt && L >= need) ? L : 0;
-  __syncthreads();
-  // inclusive prefix sums of the eligible lengths (Hillis-Steele)
-  for (int o = 1; o < GK_HC_MAX; o <<= 1) {
-    const int64_t a = t >= o ? pre[t - o] : 0;
-    __syncthreads();
-    pre[t] += a;
-    __syncthreads();
-  }
-  const int64_t budget = budget_factor * lmax;
-  const bool take = on && t < cnt && L >= need && pre[t] <= budget;
-  // a prefix: count it with a block-wide ballot of `take`
-  __shared__ int32_t k;
-  if (t == 0) k = 0;
-  __syncthreads();
-  if (take) {
-    recs[t] = GKHostChainRec{s, xo, L, list_n[t], st.sum[s], st.avg[s], st.mn[s], st.mx[s]};
-    atomicAdd(&k, 1);
-  }
-  __syncthreads();
-  if (t == 0) *hc_count = k;
-}
-
-// The join of an asynchronous host walk (round 4): one thread waits until the
-// set's host worker has published this call's sequence number in the pinned
-// flag word ((seq << 2) | 1 done / 2 failed; gk_capi.cpp hc_worker), with a
-// wall-clock bound (s_memrealtime, 100 MHz) after which the walk counts as
-// failed.  `fail` tells k_hc_apply / k_hc_fallback which of them applies the
-// picked streams' chains.  (Loads only: the flag is written by the host.)
-__global__ void k_hc_wait(const unsigned long long* __restrict__ flag, unsigned long long seq,
-                          int32_t* __restrict__ fail, unsigned long long timeout_ticks) {
-  if (threadIdx.x != 0) return;
-  const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-  int f = 1;
-  for (;;) {
-    const unsigned long long w = __hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
-    if ((w >> 2) >= seq) {
-      f = ((w >> 2) == seq && (w & 3) == 1) ? 0 : 1;
-      break;
-    }
-    if (__builtin_amdgcn_s_memrealtime() - t0 > timeout_ticks) break;
-    __builtin_amdgcn_s_sleep(127);
-  }
-  *fail = f;
-}
-
-__global__ __launch_bounds__(256) void k_hc_apply(GKState st, const GKHostChainRec* __restrict__ recs,
-                                                  const int32_t* __restrict__ hc_count,
-                                                  const int32_t* __restrict__ fail) {
-  const int t = threadIdx.x;
-  if ((fail && *fail) || t >= *hc_count) return;
-  const GKHostChainRec r = recs[t];
-  st.sum[r.s] = r.sum;
-  st.avg[r.s] = r.avg;
-  st.mn[r.s] = r.mn;
-  st.mx[r.s] = r.mx;
-}
 
 // ===========================================================================
 // k_stats_long: gk:52-59 for the streams k_lengths lists (longer than
@@ -773,9 +587,6 @@ __device__ __forceinline__ void gk_stat_step(double v, int64_t& n, double& sm, d
 // ---------------------------------------------------------------------------
 #ifndef GK_SPEC_W
 #define GK_SPEC_W 16
-#endif
-#ifndef GK_SPEC
-#define GK_SPEC 1
 #endif
 #ifndef GK_SPEC_ROUNDS
 #define GK_SPEC_ROUNDS 16
@@ -932,7 +743,6 @@ __device__ __forceinline__ void stats_long_bcast(const GKState& st, const double
   double lmn = __longlong_as_double(0x7ff0000000000000LL), lmx = -lmn;
   int64_t imn = INT64_MAX, imx = INT64_MAX;
   int64_t kb = 0;  // first value of the one-at-a-time walk
-#if GK_SPEC
   {
     constexpr int W = GK_SPEC_W;
     constexpr int SS = 64 * W;
@@ -1004,7 +814,6 @@ __device__ __forceinline__ void stats_long_bcast(const GKState& st, const double
       n += SS;  // gk:52
     }
   }
-#endif
   bcast_walk(x, xo, kb, L, n, sm, av, lmn, lmx, imn, imx, lane, buf);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -1125,36 +934,18 @@ __device__ __forceinline__ void stats_group_walk(const GKState& st, const double
   }
 }
 
-// A failed host walk: the picked streams' chains on the device instead (the
-// one-wave-per-stream walk of k_stats_long), so their _sum/_avg/_min/_max are
-// exact either way.  Exits at once when the host walk succeeded.
-__global__ __launch_bounds__(64) void k_hc_fallback(GKState st, const double* __restrict__ x,
-                                                    const int64_t* __restrict__ offs,
-                                                    const int32_t* __restrict__ list,
-                                                    const int64_t* __restrict__ list_n,
-                                                    const int32_t* __restrict__ hc_count,
-                                                    const int32_t* __restrict__ fail) {
-  __shared__ double2 buf[64];
-  if (*fail == 0) return;
-  const int k = *hc_count;
-  for (int w = blockIdx.x; w < k; w += gridDim.x) stats_long_bcast(st, x, offs, list, list_n, w, threadIdx.x, buf);
-}
-
 __global__ __launch_bounds__(64) void k_stats_long(GKState st, const double* __restrict__ x,
                                                    const int64_t* __restrict__ offs,
                                                    const int32_t* __restrict__ list,
                                                    const int64_t* __restrict__ list_n,
-                                                   const int32_t* __restrict__ count,
-                                                   const int32_t* __restrict__ hc_count, int prio) {
+                                                   const int32_t* __restrict__ count, int prio) {
   __shared__ double2 buf[64];
   __shared__ double rtile[64];
   const int lane = threadIdx.x;
   const int cnt = *count;
   if (cnt <= GK_SL_BCAST) {
     if (prio) __builtin_amdgcn_s_setprio(3);
-    // the first *hc_count streams are walked on host cores (k_hc_prep)
-    const int w0 = hc_count ? *hc_count : 0;
-    for (int w = w0 + blockIdx.x; w < cnt; w += gridDim.x) stats_long_bcast(st, x, offs, list, list_n, w, lane, buf);
+    for (int w = blockIdx.x; w < cnt; w += gridDim.x) stats_long_bcast(st, x, offs, list, list_n, w, lane, buf);
     return;
   }
   const int ngroups = (cnt + 63) / 64;
@@ -1466,7 +1257,7 @@ __device__ __forceinline__ int flush_wave(const FlushBuf& L, const int cap, cons
 
   // ---- stable order inside each gap (gk:72), then emit --------------------
   if (presorted) {
-    // values arrive in (value, insertion index) order (k_presort): the rank
+    // values arrive in (value, insertion index) order (k_presort_reg): the rank
     // inside the gap is the position minus the gap's base
 #pragma unroll
     for (int r = 0; r < VPL; ++r) {
@@ -1864,7 +1655,7 @@ __global__ __launch_bounds__(64) void k_ingest(GKState st, const double* __restr
   for (; w < total;) {
     const int64_t s = sid(w);
     const bool from_prio = w < npri;
-    // presorted automatic-flush batches of this stream (k_presort), or none
+    // presorted automatic-flush batches of this stream (k_presort_reg), or none
     const int64_t wso = (from_prio && prio_ws) ? rfl64(prio_ws[w + skip]) : -1;
     const int64_t wn = grab();
     const int32_t scls = __builtin_amdgcn_readfirstlane(hv.cls);
@@ -1956,7 +1747,7 @@ __global__ __launch_bounds__(64) void k_ingest(GKState st, const double* __restr
     // loaded one flush ahead: their HBM latency hides under the current
     // flush's LDS work.
     double xv[VPL];
-    // presorted batch b lives at psort + wso + b*P (k_presort, same values)
+    // presorted batch b lives at psort + wso + b*P (k_presort_reg, same values)
     const double* __restrict__ sb = wso >= 0 ? psort + wso : nullptr;
     if (ok && used + need <= Lx) {
       if (sb) {
@@ -2085,7 +1876,7 @@ __global__ __launch_bounds__(64) void k_ingest(GKState st, const double* __restr
 // *wg_count entries of the long list (k_long_prep: presorted streams with
 // at least 1/GK_PRESORT_REL of the longest one's flushes, at most
 // GK_WG_MAX); class-0 sets of the 2048 class (128 < P <= 1024) only.
-// Batches arrive presorted (k_presort); a batch that is not (the call's
+// Batches arrive presorted (k_presort_reg); a batch that is not (the call's
 // final partial flush) is sorted here by (value, insertion index) first.
 // The fused query of these streams is answered after the join by
 // k_query_list (their _min/_max are final only then), so none here.
@@ -2130,24 +1921,16 @@ struct WgLDS {
 #define GK_WG_GO_TICKS 100000000ull  // 1 s of s_memrealtime (100 MHz)
 #endif
 
-// The workgroup flush's value table in BFS (Eytzinger) order (GK_WG_EYTZ):
+// The workgroup flush's value table in BFS (Eytzinger) order:
 // sorted position j (0-based) of a table padded to 2^H - 1 entries lives at
 // node (j + 1 + 2^H) >> (ctz(j + 1) + 1), the root at 1.  A search level's
 // probes are then one contiguous row of nodes (2^l of them), so lanes with
 // different values hit consecutive slots -- distinct LDS banks -- where the
 // sorted layout's probes of a deep level are 2^(H-l) slots apart and share
 // one bank (the 423 conflict cycles per wave and flush of round 5).
-#ifndef GK_WG_EYTZ
-#define GK_WG_EYTZ 1
-#endif
 __device__ __forceinline__ int wg_slot(int j, int H) {
-#if GK_WG_EYTZ
   const int p1 = j + 1;
   return (p1 + (1 << H)) >> (__builtin_ctz((unsigned)p1) + 1);
-#else
-  (void)H;
-  return j;
-#endif
 }
 // tree height of a table of E entries: its padded size is pow2_above(E) - 1
 __device__ __forceinline__ int wg_height(int E) { return 32 - __clz(E); }
@@ -2302,7 +2085,6 @@ __device__ int flush_wg(WgLDS& L, const int cur, const int E, double (&xv)[GK_WG
   int xg[GK_WG_VPT];
   uint32_t slot[GK_WG_VPT];  // an unsorted value's member slot in its gap
   for (int pass = 0;; ++pass) {
-#if GK_WG_EYTZ
     {
       const int H = wg_height(E);
 #pragma unroll
@@ -2317,19 +2099,6 @@ __device__ int flush_wg(WgLDS& L, const int cur, const int E, double (&xv)[GK_WG
 #pragma unroll
       for (int r = 0; r < GK_WG_VPT; ++r) xg[r] = min(xg[r] - (1 << H), E);
     }
-#else
-#pragma unroll
-    for (int r = 0; r < GK_WG_VPT; ++r) xg[r] = 0;
-    for (int step = gk_pow2_above(E) >> 1; step > 0; step >>= 1) {
-      double tt[GK_WG_VPT];
-#pragma unroll
-      for (int r = 0; r < GK_WG_VPT; ++r) tt[r] = tv[xg[r] + step - 1];
-#pragma unroll
-      for (int r = 0; r < GK_WG_VPT; ++r) xg[r] += (tt[r] <= xv[r]) ? step : 0;
-    }
-#pragma unroll
-    for (int r = 0; r < GK_WG_VPT; ++r) xg[r] = min(xg[r], E);
-#endif
     if (pass > 0) {  // (the re-search of a sorted batch: counts start over)
       for (int j = t; j <= E; j += GK_WG_T) gpk[j] = 0u;
       __syncthreads();
@@ -2797,7 +2566,7 @@ __global__ __launch_bounds__(GK_WG_T) void k_ingest_wg(GKState st, const double*
     int64_t used = 0;
     int64_t need = P - (n % P);  // adds until n hits the next multiple of P (gk:60)
     bool flushed = false;
-    // presorted batch b of this call at psort + wso + b*P (k_presort)
+    // presorted batch b of this call at psort + wso + b*P (k_presort_reg)
     const double* __restrict__ sb = wso >= 0 ? psort + wso : nullptr;
     double xv[GK_WG_VPT];
     // the next batch is loaded one flush ahead (its HBM latency under the
@@ -2879,7 +2648,7 @@ __global__ __launch_bounds__(GK_WG_T) void k_ingest_wg(GKState st, const double*
       p = 0;
       need = P;
       flushed = true;
-      if (sb) sb += P;  // batch b at wso + b*P (k_presort)
+      if (sb) sb += P;  // batch b at wso + b*P (k_presort_reg)
       GK_BMARK(7);
     }
     (void)flushed;
@@ -3620,12 +3389,18 @@ __device__ __forceinline__ void sort128_2(double (&a)[2], int lane) {
 }
 
 // ===========================================================================
-// k_presort_reg (round 4): the presort of long streams' flush batches, one
-// WAVE per batch, in registers.  k_presort sorts a 1024-key batch with 256
-// threads through LDS (55 stages, two compare-exchanges per thread and stage
-// plus a barrier each): cfg5's 378k batches took 13.6 ms ahead of the
-// critical stream's ingest.  Here element e = lane*16 + r of the (padded)
-// batch lives in register a[r] of its lane; the bitonic network is run in the
+// k_presort_reg (round 4): the batch of every automatic flush of a listed
+// long stream (list_ws >= 0), sorted by (value, insertion index) -- Python's
+// stable sorted() of gk:71-72 -- into its workspace slot, ahead of k_ingest,
+// so that the flush (sequential per stream, on the critical path of long
+// streams) skips its in-gap ranking.  Batch 0 is the pre-call pending values
+// followed by the first `need` values; batch b > 0 is the next P values.
+// One WAVE per batch (global batch id -> stream by binary search over
+// list_b0), in registers: a 256-thread bitonic sort through LDS (55 stages
+// of two compare-exchanges per thread plus a barrier each) took 13.6 ms for
+// cfg5's 378k batches, ahead of the critical stream's ingest.  Element
+// e = lane*16 + r of the (padded) batch lives in register a[r] of its lane;
+// the bitonic network is run in the
 // form whose compare-exchanges always keep the minimum at the lower position
 // (a merge of two ascending runs of KB/2 = a mirror stage e ^ (KB-1), then
 // half-cleaners e ^ J): distances below 16 are inside a lane (one compare and
@@ -3779,7 +3554,9 @@ __device__ void presort_reg_range(const GKState& st, const double* __restrict__ 
                                   const int lane, const bool skip0) {
   const int64_t total = list_b0[cnt];
   const int P = st.P;
-  // a contiguous range of global batches per wave (as k_presort)
+  // a contiguous range of global batches per wave: one binary search for its
+  // first stream slot, then the slot advances along the (ascending) list_b0
+  // -- a search per batch was ~10 dependent global loads
   const int64_t g0 = total * blockIdx.x / gridDim.x, g1 = total * (blockIdx.x + 1) / gridDim.x;
   if (g0 >= g1) return;
   int i = 0;
@@ -5997,30 +5774,23 @@ hipError_t gk_launch_stats_short(const GKState& st, const double* x, const int64
   return hipGetLastError();
 }
 
-int gk_presort_reg_grid(const GKState& st) {
-  static const int reg = getenv("GK_PRESORT_REG") ? atoi(getenv("GK_PRESORT_REG")) : 1;
-  return (reg && st.P <= 64 * GK_PS_R) ? num_cu() * 16 : 0;
-}
+int gk_presort_reg_grid(const GKState& st) { return st.P <= 64 * GK_PS_R ? num_cu() * 16 : 0; }
 
 hipError_t gk_launch_presort(const GKState& st, const double* x, const int64_t* offs, const int32_t* long_list,
                              const int64_t* long_n, const int32_t* long_count, const GKPresort& ps,
                              hipStream_t stream) {
   if (st.S <= 0 || !ps.list_ws || !ps.ws || ps.ws_cap <= 0) return hipSuccess;
-  // one wave per batch in registers (k_presort_reg, P <= 1024); GK_PRESORT_REG=0
-  // or larger batches: the LDS sort of k_presort
-  if (gk_presort_reg_grid(st) > 0)
-    hipLaunchKernelGGL(k_presort_reg, dim3((unsigned)gk_presort_reg_grid(st)), dim3(64), 0, stream, st, x, offs,
-                       long_list, long_count, long_n, (const int64_t*)ps.list_ws, (const int64_t*)ps.list_b0, ps.ws,
-                       ps.done);
-  else
-    hipLaunchKernelGGL(k_presort, dim3((unsigned)(num_cu() * 8)), dim3(256), 0, stream, st, x, offs, long_list,
-                       long_count, long_n, (const int64_t*)ps.list_ws, (const int64_t*)ps.list_b0, ps.ws);
+  // one wave per batch in registers: a workspace exists only where class 0
+  // is a capacity-class kernel, so P <= 1024 = the keys of one wave
+  const int grid = gk_presort_reg_grid(st);
+  if (grid <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_presort_reg, dim3((unsigned)grid), dim3(64), 0, stream, st, x, offs, long_list, long_count,
+                     long_n, (const int64_t*)ps.list_ws, (const int64_t*)ps.list_b0, ps.ws, ps.done);
   return hipGetLastError();
 }
 
 hipError_t gk_launch_stats_long(const GKState& st, const double* x, const int64_t* offs, const int32_t* long_list,
-                                const int64_t* long_n, const int32_t* long_count, const int32_t* hc_count,
-                                hipStream_t stream) {
+                                const int64_t* long_n, const int32_t* long_count, hipStream_t stream) {
   if (st.S <= 0) return hipSuccess;
   // the long-stream count is only known on the device: a fixed grid of waves
   // reads it (an empty list costs one short launch)
@@ -6029,40 +5799,7 @@ hipError_t gk_launch_stats_long(const GKState& st, const double* x, const int64_
   // arbitration over the co-resident ingest waves)
   static const int sl_prio = getenv("GK_SL_PRIO") ? atoi(getenv("GK_SL_PRIO")) : 1;
   hipLaunchKernelGGL(k_stats_long, dim3((unsigned)(num_cu() * 4)), dim3(64), 0, stream, st, x, offs, long_list,
-                     long_n, long_count, hc_count, sl_prio);
-  return hipGetLastError();
-}
-
-hipError_t gk_launch_hc_prep(const GKState& st, const int64_t* offs, const int32_t* long_list, const int64_t* long_n,
-                             const int32_t* long_count, int64_t min_len, int rel_pct, int64_t budget_factor,
-                             GKHostChainRec* recs, int32_t* hc_count, hipStream_t stream) {
-  static_assert(GK_HC_MAX == 256, "k_hc_prep: one thread per record");
-  if (st.S <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_hc_prep, dim3(1), dim3(GK_HC_MAX), 0, stream, st, offs, long_list, long_n, long_count, min_len,
-                     rel_pct, budget_factor, recs, hc_count);
-  return hipGetLastError();
-}
-
-hipError_t gk_launch_hc_apply(const GKState& st, const GKHostChainRec* recs, const int32_t* hc_count,
-                              const int32_t* fail, hipStream_t stream) {
-  if (st.S <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_hc_apply, dim3(1), dim3(GK_HC_MAX), 0, stream, st, recs, hc_count, fail);
-  return hipGetLastError();
-}
-
-hipError_t gk_launch_hc_wait(const unsigned long long* flag, unsigned long long seq, int32_t* fail,
-                             double timeout_s, hipStream_t stream) {
-  hipLaunchKernelGGL(k_hc_wait, dim3(1), dim3(64), 0, stream, flag, seq, fail,
-                     (unsigned long long)(timeout_s * 1e8));
-  return hipGetLastError();
-}
-
-hipError_t gk_launch_hc_fallback(const GKState& st, const double* x, const int64_t* offs, const int32_t* long_list,
-                                 const int64_t* long_n, const int32_t* hc_count, const int32_t* fail,
-                                 hipStream_t stream) {
-  if (st.S <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_hc_fallback, dim3(GK_HC_MAX), dim3(64), 0, stream, st, x, offs, long_list, long_n, hc_count,
-                     fail);
+                     long_n, long_count, sl_prio);
   return hipGetLastError();
 }
 

@@ -95,44 +95,14 @@ hipError_t gk_launch_long_prep(const GKState& st, const int64_t* offs, int32_t* 
 // gk:52-59 chains of the streams up to GK_STATS_LONG values (k_stats_short; the
 // long ones are k_stats_long's), when class 0 is not the small class
 hipError_t gk_launch_stats_short(const GKState& st, const double* x, const int64_t* offs, hipStream_t stream);
-// k_presort over the plan k_long_prep wrote (no-op without a workspace)
-// k_presort_reg's grid (waves); k_ingest_wg compares *ps.done with it
+// the presort (k_presort_reg) over the plan k_long_prep wrote (no-op without
+// a workspace), and its grid (waves); k_ingest_wg compares *ps.done with it
 int gk_presort_reg_grid(const GKState& st);
 hipError_t gk_launch_presort(const GKState& st, const double* x, const int64_t* offs, const int32_t* long_list,
                              const int64_t* long_n, const int32_t* long_count, const GKPresort& ps,
                              hipStream_t stream);
-// hc_count (device, may be NULL): the first *hc_count list entries are
-// walked on host cores (gk_launch_hc_prep) and skipped here
 hipError_t gk_launch_stats_long(const GKState& st, const double* x, const int64_t* offs, const int32_t* long_list,
-                                const int64_t* long_n, const int32_t* long_count, const int32_t* hc_count,
-                                hipStream_t stream);
-// Host-walked chains: the longest streams of the sorted
-// long list whose gk:52-59 chains run on host cores.  One record per stream:
-// the pre-call state from gk_launch_hc_prep, the final one written back by
-// the host and applied by gk_launch_hc_apply.
-struct GKHostChainRec {
-  int64_t s, xo, len, n;
-  double sum, avg, mn, mx;
-};
-#define GK_HC_MAX 256
-// takes list entries while len >= min_len and len >= rel_pct % of the
-// longest, at most GK_HC_MAX of them and budget_factor x (the longest length)
-// values in all, and only when the list is walked one wave per stream
-// (<= GK_SL_BCAST streams); min_len <= 0: none
-hipError_t gk_launch_hc_prep(const GKState& st, const int64_t* offs, const int32_t* long_list, const int64_t* long_n,
-                             const int32_t* long_count, int64_t min_len, int rel_pct, int64_t budget_factor,
-                             GKHostChainRec* recs, int32_t* hc_count, hipStream_t stream);
-// fail (device, may be NULL): set by gk_launch_hc_wait; nonzero = the host
-// walk failed and gk_launch_hc_fallback walks the picked streams instead
-hipError_t gk_launch_hc_apply(const GKState& st, const GKHostChainRec* recs, const int32_t* hc_count,
-                              const int32_t* fail, hipStream_t stream);
-// waits (one thread, s_sleep) until *flag >> 2 >= seq, at most timeout_s
-// seconds; *fail = 0 iff the flag is (seq << 2) | 1
-hipError_t gk_launch_hc_wait(const unsigned long long* flag, unsigned long long seq, int32_t* fail,
-                             double timeout_s, hipStream_t stream);
-hipError_t gk_launch_hc_fallback(const GKState& st, const double* x, const int64_t* offs, const int32_t* long_list,
-                                 const int64_t* long_n, const int32_t* hc_count, const int32_t* fail,
-                                 hipStream_t stream);
+                                const int64_t* long_n, const int32_t* long_count, hipStream_t stream);
 // quantiles of the listed streams from their committed tables (after the
 // join); qfix: also resolve the _min/_max markers of a small-class launch
 // that carried the stats role (every stream's answers)

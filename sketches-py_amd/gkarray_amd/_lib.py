@@ -88,7 +88,6 @@ SYMBOLS = {
     "gk_flush_period": (_INT, [_P]),
     "gk_capacity": (_INT, [_P, _INT]),
     "gk_num_promoted": (_I64, [_P]),
-    "gk_host_chains_taken": (_I64, [_P]),
     "gk_timing_enable": (_INT, [_P, _INT]),
     "gk_timing_read": (_INT, [_P, ctypes.POINTER(_D), ctypes.POINTER(_D), ctypes.POINTER(_I64)]),
 }

@@ -1,6 +1,6 @@
 """Presorted flush batches of long streams (P > 128; DESIGN.md section 5, long
 streams): k_long_prep plans the batches of the streams within a quarter of
-the longest one's flush count, k_presort sorts them (value, then insertion
+the longest one's flush count, k_presort_reg sorts them (value, then insertion
 index: gk:71-72's stable sorted()) ahead of the ingest launch, and the flush
 of a presorted batch places each value at its rank directly; the other long
 streams flush unsorted.  Results never depend on which streams were planned.
@@ -11,6 +11,11 @@ make every call's batch 0 start with them; every third stream holds rounded
 values (ties: the stable order decides).  Every call's whole state (tables,
 pending values, n/min/max/sum/avg) and the fused quantiles are compared bit
 for bit with the oracle.
+
+k_presort_reg (one wave per batch, 16 keys per lane) is the only presort, so
+the two edge periods run beside P = 1001: P = 129, the smallest period with a
+presort (class 0 is the 2048-entry class from P > 128), and P = 1024, every
+key of every lane in use.
 """
 import numpy as np
 import pytest
@@ -24,11 +29,17 @@ pytestmark = pytest.mark.gpu
 QS = [0.01, 0.5, 0.9, 0.99]
 
 
-@pytest.mark.parametrize("seed", [0, 1])
-def test_presorted_batches_across_calls(gpu_device, seed):
-    S, eps = 48, 0.001  # P = 1001: class 0 is the 2048-entry LDS class
+@pytest.mark.parametrize("eps,seed", [
+    pytest.param(0.001, 0, id="0"),  # P = 1001: class 0 is the 2048-entry LDS class
+    pytest.param(0.001, 1, id="1"),
+    pytest.param(1 / 128.5, 0, id="P129"),
+    pytest.param(1 / 1023.5, 0, id="P1024"),
+])
+def test_presorted_batches_across_calls(gpu_device, eps, seed):
+    S = 48
     rng = np.random.default_rng(1000 + seed)
     ss = _ss(S, eps, gpu_device)
+    assert ss.flush_period == int(1.0 / eps) + 1
     o = OracleSet(S, eps)
     for call in range(4):
         lens = rng.integers(0, 45_000, S)

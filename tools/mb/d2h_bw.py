@@ -1,5 +1,5 @@
 """D2H bandwidth on the box: one large pinned copy, and 16 threads copying
-2/8/32 MiB chunks on their own streams (host-walked chains' copy pattern)."""
+2/8/32 MiB chunks on their own streams (the copy pattern of the removed host-walked chains)."""
 import threading
 import time
 
