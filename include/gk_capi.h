@@ -29,7 +29,8 @@
  *    gk_reset_select, gk_stats_select, gk_ranks, gk_ranks_select,
  *    gk_merge_compress, gk_import, gk_save / gk_load, gk_pack_select_bytes,
  *    gk_pack_select, gk_unpack_select and gk_num_promoted synchronise before
- *    returning.
+ *    returning; so do the key directory's calls (gk_dir_*, an object of its
+ *    own).
  *  - Limits.  Any finite eps > 0 with int(1/eps)+1 < 2^24 is accepted (the
  *    reference: any eps; eps > 1 gives a flush period of 1, gk:60); tables grow through capacity classes up to 2^27 entries per
  *    stream (the last classes are allocated on first use).  One stream may
@@ -463,6 +464,80 @@ int gk_fold_packed(gk_set* dst, const void* const* bufs, int nbufs, void* stream
 int gk_pack_select_bytes(gk_set* set, const int32_t* ids, int64_t count, int64_t* bytes, void* stream);
 int gk_pack_select(gk_set* set, const int32_t* ids, int64_t count, void* buf, int64_t bytes, void* stream);
 int gk_unpack_select(gk_set* set, const int32_t* ids, int64_t count, const void* buf, void* stream);
+
+/* ---- key directory: int64 keys to stream ids, assigned by the engine ---------
+ * The dict of the reference's user (sketches[key] = GKArray(eps) on a key
+ * not seen before): a persistent table from int64 keys to int32 ids that
+ * looks up or inserts a whole batch of sample keys in one call.  Its ids are
+ * what gk_ingest_keyed, the gk_*_select calls, gk_pack_select and roll-up
+ * member lists take.  A directory is an object of its own, not part of a
+ * set: one directory may serve several sets.  It is insert-only; the caller
+ * compacts the id space with gk_dir_keys -> filter -> gk_dir_import.
+ *  - Memory.  `keys` (int64), `out_ids` (int32) and `out_keys` (int64) are
+ *    device memory on the directory's GPU for the GPU engine, host memory
+ *    for the CPU engine.  `num_new` is host memory.
+ *  - Count.  0 <= count <= 2^31-1, anything else is GK_E_ARG.  count == 0 is
+ *    valid with NULL arrays; a NULL array with count > 0 is GK_E_ARG.
+ *  - GK_DIR_NONE is "no key": it is never stored and always answers id -1,
+ *    gk_ingest_keyed's "not for this set".  Every other int64 value is a key.
+ *  - Synchronisation.  gk_dir_assign, gk_dir_lookup, gk_dir_keys and
+ *    gk_dir_import synchronise before returning.  A directory is not
+ *    thread-safe; its calls must be ordered on one stream.
+ *
+ * gk_dir_create: an empty directory of at most `capacity` keys, 1 <= capacity
+ *   <= 2^30 (GK_E_ARG otherwise), on HIP device `device`.
+ * gk_dir_assign is this loop over the directory d:
+ *       for i in 0 .. count-1:
+ *           k = keys[i]
+ *           if k == GK_DIR_NONE:   out_ids[i] = -1
+ *           elif k in d:           out_ids[i] = d[k]
+ *           else:                  d[k] = len(d); out_ids[i] = d[k]
+ *   New keys are numbered in order of FIRST OCCURRENCE in the batch,
+ *   continuing from gk_dir_size: every output is a function of the
+ *   directory's history and the batch alone -- not of the hash, the probe
+ *   order or the scheduling of the device's threads -- and the two engines
+ *   give identical ids.  *num_new (may be NULL) receives the number of keys
+ *   added.  GK_E_OVERFLOW if len(d) would pass `capacity`: the call is then
+ *   void and the directory exactly as before it (gk_dir_size, gk_dir_keys and
+ *   every later gk_dir_lookup / gk_dir_assign answer as if it had not
+ *   happened); out_ids is unspecified and *num_new is not written.
+ * gk_dir_lookup: read-only; out_ids[i] = d[keys[i]], or -1 for a key the
+ *   directory does not hold and for GK_DIR_NONE.
+ * gk_dir_keys: the inverse array, out_keys[id] = the key that holds id, for
+ *   id in [0, gk_dir_size); out_keys may be NULL while the directory is empty.
+ * gk_dir_import: replaces the contents with keys[i] -> i, i in [0, count)
+ *   (restore, a copy of another capacity, a compacted id space).  GK_E_ARG for
+ *   count > capacity, for a GK_DIR_NONE entry (its first index in the
+ *   message) and for a key listed twice (the first index that repeats an
+ *   earlier entry, and the key, in the message): refused BEFORE anything is
+ *   mutated -- the new contents are built in a second table that replaces the
+ *   first on success.
+ *  - Memory (per capacity).  The table has T slots, T the power of two >=
+ *    2 * capacity and at least 64; a slot holds an 8-byte key, a 4-byte id and
+ *    a 4-byte first-occurrence word (16 T bytes); the inverse array adds 8
+ *    bytes per id of `capacity`.  gk_dir_import holds two tables while it
+ *    runs.  GK_E_NOMEM is returned before anything is mutated.
+ *  - Scratch (GPU engine; owned by the directory, only grows, freed by
+ *    gk_dir_destroy).  gk_dir_assign and gk_dir_import: 8 bytes per sample
+ *    (the sample's slot and its first-occurrence flag, scanned in place into
+ *    its rank) + 8 bytes per 2048 samples (the scan's tile sums), sized for
+ *    max(count, gk_dir_size) samples so that a void call can always rebuild
+ *    the table.  gk_dir_lookup and gk_dir_keys need none.
+ *  - GK_DIR_HASH_BITS=b (environment, read by gk_dir_create; tests) confines
+ *    the keys' home slots to the last 2^b slots of the table: b = 0 makes the
+ *    table one probe chain that wraps round its end.  Not a number >= 0:
+ *    GK_E_ARG.  The hash itself is not part of the ABI. */
+typedef struct gk_dir gk_dir;
+#define GK_DIR_NONE INT64_MIN
+int gk_dir_create(int64_t capacity, int device, gk_dir** out);
+int gk_dir_destroy(gk_dir* dir);
+int64_t gk_dir_capacity(const gk_dir* dir);
+int64_t gk_dir_size(const gk_dir* dir);  /* keys assigned so far */
+int gk_dir_assign(gk_dir* dir, const int64_t* keys, int64_t count, int32_t* out_ids, int64_t* num_new,
+                  void* stream);
+int gk_dir_lookup(gk_dir* dir, const int64_t* keys, int64_t count, int32_t* out_ids, void* stream);
+int gk_dir_keys(gk_dir* dir, int64_t* out_keys, void* stream);
+int gk_dir_import(gk_dir* dir, const int64_t* keys, int64_t count, void* stream);
 
 /* Introspection for tests and benchmarks. */
 int64_t gk_num_streams(const gk_set* set);

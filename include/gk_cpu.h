@@ -9,7 +9,8 @@
  *    no-op), `device` of gk_create is ignored;
  *  - there are no capacity classes: tables and pending buffers grow without
  *    bound, any finite eps > 0 is accepted, GK_E_OVERFLOW never occurs
- *    (gk_unpack_select included: a table of any size is installed);
+ *    (gk_unpack_select included: a table of any size is installed) -- except
+ *    from gk_dir_assign, whose capacity rule is the same in both engines;
  *  - streams are processed in parallel on host threads (each stream strictly
  *    in insertion order): GK_CPU_THREADS (environment) or gk_cpu_set_threads,
  *    default = the CPUs this process may run on.

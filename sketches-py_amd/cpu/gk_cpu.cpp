@@ -28,6 +28,7 @@
 
 #include "gk_cpu.h"
 #include "gk_checks.h"
+#include "gk_dirhash.h"
 #include "gk_format.h"
 #include "gk_pack.h"
 
@@ -1109,6 +1110,157 @@ int gk_unpack_select(gk_set* h, const int32_t* ids, int64_t count, const void* b
     return fail(GK_E_NOMEM, "unpack of %lld stream(s) failed", (long long)count);
   }
   for (int64_t k = 0; k < count; ++k) h->st[ids[k]] = std::move(fresh[(size_t)k]);
+  return GK_OK;
+}
+
+// ---- key directory: the loop of gk_capi.h over an open-addressing table -------
+}  // extern "C"
+
+namespace {
+// linear probing over T slots (gk_dirhash.h: geometry, hash and the
+// GK_DIR_HASH_BITS switch are the device engine's)
+struct DirTable {
+  std::vector<int64_t> keys;  // GK_DIR_NONE = empty
+  std::vector<int32_t> ids;
+  std::vector<int64_t> key_of_id;
+  uint32_t T = 0;
+  GKDirHome home = {};
+
+  void clear(int64_t slots) {
+    T = (uint32_t)slots;
+    keys.assign((size_t)slots, GK_DIR_NONE);
+    ids.assign((size_t)slots, -1);
+    key_of_id.clear();
+  }
+  // the slot of k, or the empty slot where its probe ends (T full slots: -1)
+  int64_t find(int64_t k) const {
+    uint32_t slot = gk_dir_home(home, gk_dir_mix((uint64_t)k));
+    for (uint32_t it = 0; it < T; ++it) {
+      if (keys[slot] == k || keys[slot] == GK_DIR_NONE) return slot;
+      slot = (slot + 1) & (T - 1);
+    }
+    return -1;
+  }
+  // d[k] = len(d) for a key the table does not hold (slot: find's answer)
+  void add(int64_t slot, int64_t k) {
+    keys[(size_t)slot] = k;
+    ids[(size_t)slot] = (int32_t)key_of_id.size();
+    key_of_id.push_back(k);
+  }
+};
+}  // namespace
+
+struct gk_dir {
+  int64_t capacity = 0;
+  DirTable t;
+};
+
+extern "C" {
+
+int gk_dir_create(int64_t capacity, int device, gk_dir** out) {
+  (void)device;
+  int rc = check_dir_create(capacity, out);
+  if (rc) return rc;
+  GKDirHome home;
+  const int64_t T = gk_dir_slots(capacity);
+  if (!gk_dir_home_from_env(T, &home))
+    return fail(GK_E_ARG, "GK_DIR_HASH_BITS=%s: a number >= 0", getenv("GK_DIR_HASH_BITS"));
+  try {
+    gk_dir* d = new gk_dir();
+    d->capacity = capacity;
+    d->t.home = home;
+    d->t.clear(T);
+    *out = d;
+  } catch (...) {
+    return fail(GK_E_NOMEM, "directory: no memory for a table of %lld slots", (long long)T);
+  }
+  return GK_OK;
+}
+
+int gk_dir_destroy(gk_dir* d) {
+  delete d;
+  return GK_OK;
+}
+
+int64_t gk_dir_capacity(const gk_dir* d) { return d ? d->capacity : -1; }
+int64_t gk_dir_size(const gk_dir* d) { return d ? (int64_t)d->t.key_of_id.size() : -1; }
+
+int gk_dir_assign(gk_dir* d, const int64_t* keys, int64_t count, int32_t* out_ids, int64_t* num_new, void* stream) {
+  (void)stream;
+  int rc = check_dir_args(d, keys, count, out_ids, true);
+  if (rc) return rc;
+  DirTable& t = d->t;
+  const int64_t size0 = (int64_t)t.key_of_id.size();
+  for (int64_t i = 0; i < count; ++i) {
+    const int64_t k = keys[i];
+    if (k == GK_DIR_NONE) {
+      out_ids[i] = -1;
+      continue;
+    }
+    const int64_t slot = t.find(k);
+    if (slot >= 0 && t.keys[(size_t)slot] == k) {
+      out_ids[i] = t.ids[(size_t)slot];
+      continue;
+    }
+    if ((int64_t)t.key_of_id.size() == d->capacity) {
+      // void call: the table is insert-only, so it is rebuilt from the ids it held before
+      std::vector<int64_t> old(t.key_of_id.begin(), t.key_of_id.begin() + size0);
+      t.clear(t.T);
+      for (int64_t k0 : old) t.add(t.find(k0), k0);
+      return fail_dir_overflow(d->capacity, size0);
+    }
+    t.add(slot, k);  // (size < capacity <= T / 2: find met an empty slot)
+    out_ids[i] = t.ids[(size_t)slot];
+  }
+  if (num_new) *num_new = (int64_t)t.key_of_id.size() - size0;
+  return GK_OK;
+}
+
+int gk_dir_lookup(gk_dir* d, const int64_t* keys, int64_t count, int32_t* out_ids, void* stream) {
+  (void)stream;
+  int rc = check_dir_args(d, keys, count, out_ids, true);
+  if (rc) return rc;
+  const DirTable& t = d->t;
+  for (int64_t i = 0; i < count; ++i) {
+    const int64_t k = keys[i];
+    const int64_t slot = k == GK_DIR_NONE ? -1 : t.find(k);
+    out_ids[i] = (slot >= 0 && t.keys[(size_t)slot] == k) ? t.ids[(size_t)slot] : -1;
+  }
+  return GK_OK;
+}
+
+int gk_dir_keys(gk_dir* d, int64_t* out_keys, void* stream) {
+  (void)stream;
+  int rc = check_dir(d);
+  if (rc) return rc;
+  if (d->t.key_of_id.empty()) return GK_OK;
+  if (!out_keys) return fail(GK_E_ARG, "out_keys is null");
+  std::copy(d->t.key_of_id.begin(), d->t.key_of_id.end(), out_keys);
+  return GK_OK;
+}
+
+int gk_dir_import(gk_dir* d, const int64_t* keys, int64_t count, void* stream) {
+  (void)stream;
+  int rc = check_dir_args(d, keys, count, nullptr, false);
+  if (rc) return rc;
+  if (count > d->capacity) return fail_dir_import_count(count, d->capacity);
+  for (int64_t i = 0; i < count; ++i)
+    if (keys[i] == GK_DIR_NONE) return fail_dir_import_none(i);
+  // built in a second table that replaces the first on success
+  DirTable nt;
+  nt.home = d->t.home;
+  try {
+    nt.clear(d->t.T);
+    nt.key_of_id.reserve((size_t)count);
+  } catch (...) {
+    return fail(GK_E_NOMEM, "directory: no memory for a second table");
+  }
+  for (int64_t i = 0; i < count; ++i) {
+    const int64_t slot = nt.find(keys[i]);
+    if (nt.keys[(size_t)slot] == keys[i]) return fail_dir_import_repeat(i, keys[i]);
+    nt.add(slot, keys[i]);
+  }
+  d->t = std::move(nt);
   return GK_OK;
 }
 

@@ -2178,6 +2178,209 @@ int gk_unpack_select(gk_set* h, const int32_t* ids, int64_t count, const void* b
   return GK_OK;
 }
 
+// ---- key directory (gk_dir.hip) ----------------------------------------------
+}  // extern "C"
+
+struct gk_dir {
+  int64_t capacity = 0;
+  int64_t size = 0;  // keys assigned so far
+  int device = 0;
+  GKDirTable t = {};
+  // scratch of assign / import (only grows): per sample its slot and its flag,
+  // scanned in place into its rank; the scan's tile sums; the control words
+  uint32_t* d_slot = nullptr;
+  uint32_t* d_flag = nullptr;
+  unsigned long long* d_sums = nullptr;
+  int64_t scratch_n = 0;
+  unsigned long long* d_ctl = nullptr;  // GK_DIR_CTL_WORDS
+};
+
+namespace {
+
+void dir_free_table(GKDirTable* t) {
+  for (void* p : {(void*)t->keys, (void*)t->meta, (void*)t->key_of_id})
+    if (p) (void)hipFree(p);
+  t->keys = nullptr;
+  t->meta = nullptr;
+  t->key_of_id = nullptr;
+}
+
+// a cleared table of the geometry of `like` (pointers of *t are overwritten)
+int dir_new_table(const GKDirTable& like, GKDirTable* t, hipStream_t s) {
+  *t = like;
+  t->keys = nullptr;
+  t->meta = nullptr;
+  t->key_of_id = nullptr;
+  const size_t T = (size_t)like.T;
+  if (!renew_dev(&t->keys, T * sizeof(unsigned long long)) || !renew_dev(&t->meta, T * sizeof(uint2)) ||
+      !renew_dev(&t->key_of_id, (size_t)like.capacity * sizeof(int64_t))) {
+    dir_free_table(t);
+    return fail(GK_E_NOMEM, "directory: no device memory for a table of %zu slots", T);
+  }
+  HIP_TRY(gk_launch_dir_clear(*t, s));
+  return GK_OK;
+}
+
+int dir_ensure_scratch(gk_dir* d, int64_t n) {
+  if (n <= d->scratch_n) return GK_OK;
+  HIP_TRY(hipDeviceSynchronize());  // (nothing of this directory is in flight: its calls synchronise)
+  d->scratch_n = 0;
+  if (!renew_dev(&d->d_slot, (size_t)n * sizeof(uint32_t)) || !renew_dev(&d->d_flag, (size_t)n * sizeof(uint32_t)) ||
+      !renew_dev(&d->d_sums, (size_t)gk_scan_sums(n) * sizeof(unsigned long long)))
+    return fail(GK_E_NOMEM, "directory: no device memory for the scratch of %lld samples", (long long)n);
+  d->scratch_n = n;
+  return GK_OK;
+}
+
+// The control words of the call that just ran on s, after a synchronise.
+int dir_read_ctl(gk_dir* d, unsigned long long* ctl, hipStream_t s) {
+  HIP_TRY(hipMemcpyAsync(ctl, d->d_ctl, GK_DIR_CTL_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return GK_OK;
+}
+
+// keys[i] -> i into the cleared table t (import, and the rebuild after a void call)
+int dir_fill(gk_dir* d, const GKDirTable& t, const int64_t* keys, int64_t count, hipStream_t s) {
+  HIP_TRY(hipMemsetAsync(d->d_ctl, 0, GK_DIR_CTL_WORDS * sizeof(unsigned long long), s));
+  HIP_TRY(gk_launch_dir_insert(t, keys, count, d->d_slot, d->d_ctl, s));
+  HIP_TRY(gk_launch_dir_number(t, keys, d->d_slot, nullptr, count, 0, d->d_ctl, s));
+  return GK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gk_dir_create(int64_t capacity, int device, gk_dir** out) {
+  int rc = check_dir_create(capacity, out);
+  if (rc) return rc;
+  GKDirTable like = {};
+  like.T = (uint32_t)gk_dir_slots(capacity);
+  like.capacity = capacity;
+  if (!gk_dir_home_from_env((int64_t)like.T, &like.home))
+    return fail(GK_E_ARG, "GK_DIR_HASH_BITS=%s: a number >= 0", getenv("GK_DIR_HASH_BITS"));
+  int dev_count = 0;
+  if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count <= 0) return fail(GK_E_HIP, "no HIP device available");
+  if (device < 0 || device >= dev_count) return fail(GK_E_ARG, "device %d out of range", device);
+  HIP_TRY(hipSetDevice(device));
+  gk_dir* d = new gk_dir();
+  d->capacity = capacity;
+  d->device = device;
+  rc = dir_new_table(like, &d->t, nullptr);
+  if (!rc && !renew_dev(&d->d_ctl, GK_DIR_CTL_WORDS * sizeof(unsigned long long)))
+    rc = fail(GK_E_NOMEM, "directory: no device memory for the control words");
+  if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(GK_E_HIP, "directory: clearing the table failed");
+  if (rc) {
+    gk_dir_destroy(d);
+    return rc;
+  }
+  *out = d;
+  return GK_OK;
+}
+
+int gk_dir_destroy(gk_dir* d) {
+  if (!d) return GK_OK;
+  (void)hipDeviceSynchronize();
+  dir_free_table(&d->t);
+  for (void* p : {(void*)d->d_slot, (void*)d->d_flag, (void*)d->d_sums, (void*)d->d_ctl})
+    if (p) (void)hipFree(p);
+  delete d;
+  return GK_OK;
+}
+
+int64_t gk_dir_capacity(const gk_dir* d) { return d ? d->capacity : -1; }
+int64_t gk_dir_size(const gk_dir* d) { return d ? d->size : -1; }
+
+int gk_dir_assign(gk_dir* d, const int64_t* keys, int64_t count, int32_t* out_ids, int64_t* num_new, void* stream) {
+  int rc = check_dir_args(d, keys, count, out_ids, true);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (count == 0) {
+    HIP_TRY(hipStreamSynchronize(s));
+    if (num_new) *num_new = 0;
+    return GK_OK;
+  }
+  rc = dir_ensure_scratch(d, std::max(count, d->size));
+  if (rc) return rc;
+  HIP_TRY(hipMemsetAsync(d->d_ctl, 0, GK_DIR_CTL_WORDS * sizeof(unsigned long long), s));
+  HIP_TRY(hipMemsetAsync(d->d_ctl + GK_DIR_CTL_IDLE, 1, sizeof(unsigned long long), s));  // (any non-zero word)
+  HIP_TRY(gk_launch_dir_insert(d->t, keys, count, d->d_slot, d->d_ctl, s));
+  HIP_TRY(gk_launch_dir_flag(d->t, d->d_slot, count, d->d_flag, d->d_ctl, s));
+  static_assert(GK_KG_BAD == 0, "the scan reads its skip word at index GK_KG_BAD");
+  HIP_TRY(gk_launch_scan_u32(d->d_flag, count, d->d_sums, d->d_ctl + GK_DIR_CTL_IDLE, d->d_ctl + GK_DIR_CTL_NEW, s));
+  HIP_TRY(gk_launch_dir_number(d->t, keys, d->d_slot, d->d_flag, count, d->size, d->d_ctl, s));
+  HIP_TRY(gk_launch_dir_lookup(d->t, keys, d->d_slot, count, out_ids, s));
+  unsigned long long ctl[GK_DIR_CTL_WORDS];
+  rc = dir_read_ctl(d, ctl, s);
+  if (rc) return rc;
+  if (ctl[GK_DIR_CTL_OVF]) {
+    // void call: claimed slots cannot be released (insert-only table), so the
+    // table is rebuilt from the inverse array, which no void call has touched
+    HIP_TRY(gk_launch_dir_clear(d->t, s));
+    rc = dir_fill(d, d->t, d->t.key_of_id, d->size, s);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    return fail_dir_overflow(d->capacity, d->size);
+  }
+  d->size += (int64_t)ctl[GK_DIR_CTL_NEW];
+  if (num_new) *num_new = (int64_t)ctl[GK_DIR_CTL_NEW];
+  return GK_OK;
+}
+
+int gk_dir_lookup(gk_dir* d, const int64_t* keys, int64_t count, int32_t* out_ids, void* stream) {
+  int rc = check_dir_args(d, keys, count, out_ids, true);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(gk_launch_dir_lookup(d->t, keys, nullptr, count, out_ids, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return GK_OK;
+}
+
+int gk_dir_keys(gk_dir* d, int64_t* out_keys, void* stream) {
+  int rc = check_dir(d);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (d->size > 0) {
+    if (!out_keys) return fail(GK_E_ARG, "out_keys is null");
+    HIP_TRY(hipMemcpyAsync(out_keys, d->t.key_of_id, (size_t)d->size * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  return GK_OK;
+}
+
+int gk_dir_import(gk_dir* d, const int64_t* keys, int64_t count, void* stream) {
+  int rc = check_dir_args(d, keys, count, nullptr, false);
+  if (rc) return rc;
+  if (count > d->capacity) return fail_dir_import_count(count, d->capacity);
+  hipStream_t s = (hipStream_t)stream;
+  rc = dir_ensure_scratch(d, std::max(count, d->size));
+  if (rc) return rc;
+  GKDirTable nt;
+  rc = dir_new_table(d->t, &nt, s);
+  unsigned long long ctl[GK_DIR_CTL_WORDS] = {};
+  if (!rc) rc = dir_fill(d, nt, keys, count, s);
+  if (!rc) rc = dir_read_ctl(d, ctl, s);
+  if (!rc && ctl[GK_DIR_CTL_NONE]) rc = fail_dir_import_none(count - (int64_t)ctl[GK_DIR_CTL_NONE]);
+  if (!rc && ctl[GK_DIR_CTL_DUP]) {
+    const int64_t idx = count - (int64_t)ctl[GK_DIR_CTL_DUP];
+    int64_t key = 0;
+    if (hipMemcpy(&key, keys + idx, sizeof(key), hipMemcpyDeviceToHost) != hipSuccess)
+      rc = fail(GK_E_HIP, "directory: device-to-host copy failed");
+    else
+      rc = fail_dir_import_repeat(idx, key);
+  }
+  if (!rc && ctl[GK_DIR_CTL_OVF]) rc = fail(GK_E_HIP, "directory: import ran out of slots");  // (count <= capacity: never)
+  if (rc) {
+    (void)hipStreamSynchronize(s);
+    dir_free_table(&nt);
+    return rc;
+  }
+  dir_free_table(&d->t);
+  d->t = nt;
+  d->size = count;
+  return GK_OK;
+}
+
 int64_t gk_num_streams(const gk_set* h) { return h ? h->S : -1; }
 double gk_eps(const gk_set* h) { return h ? h->eps : 0.0; }
 int gk_flush_period(const gk_set* h) { return h ? h->P : -1; }

@@ -99,4 +99,45 @@ int check_record_args(const double* v, const int32_t* g, const int32_t* d, const
   return GK_OK;
 }
 
+// ---- key directory (gk_dir_*) ----
+int check_dir(const gk_dir* d) {
+  if (!d) return fail(GK_E_ARG, "null directory");
+  return GK_OK;
+}
+
+int check_dir_create(int64_t capacity, gk_dir** out) {
+  if (!out) return fail(GK_E_ARG, "out is null");
+  *out = nullptr;
+  if (capacity < 1 || capacity > ((int64_t)1 << 30))
+    return fail(GK_E_ARG, "capacity %lld outside [1, 2^30]", (long long)capacity);
+  return GK_OK;
+}
+
+// gk_dir_assign / gk_dir_lookup (out_ids wanted) and gk_dir_import
+int check_dir_args(const gk_dir* d, const int64_t* keys, int64_t count, const int32_t* out_ids, bool want_out) {
+  int rc = check_dir(d);
+  if (!rc) rc = check_count(count);
+  if (rc) return rc;
+  if (count > 0 && !keys) return fail(GK_E_ARG, "keys is null");
+  if (count > 0 && want_out && !out_ids) return fail(GK_E_ARG, "out_ids is null");
+  return GK_OK;
+}
+
+int fail_dir_overflow(int64_t capacity, int64_t size) {
+  return fail(GK_E_OVERFLOW, "the batch's new keys do not fit the directory (capacity %lld, %lld assigned): call void",
+              (long long)capacity, (long long)size);
+}
+
+int fail_dir_import_count(int64_t count, int64_t capacity) {
+  return fail(GK_E_ARG, "import of %lld keys into a directory of capacity %lld", (long long)count, (long long)capacity);
+}
+
+int fail_dir_import_none(int64_t index) {
+  return fail(GK_E_ARG, "keys[%lld] is GK_DIR_NONE", (long long)index);
+}
+
+int fail_dir_import_repeat(int64_t index, int64_t key) {
+  return fail(GK_E_ARG, "keys[%lld] repeats key %lld", (long long)index, (long long)key);
+}
+
 }  // namespace

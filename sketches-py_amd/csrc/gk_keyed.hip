@@ -360,6 +360,11 @@ hipError_t gk_launch_scan_i64(int64_t* a, int64_t n, unsigned long long* sums, h
   return scan_in_place<int64_t>(a, n, sums, nullptr, nullptr, stream);
 }
 
+hipError_t gk_launch_scan_u32(uint32_t* a, int64_t n, unsigned long long* sums, const unsigned long long* skip,
+                              unsigned long long* total_out, hipStream_t stream) {
+  return scan_in_place<uint32_t>(a, n, sums, skip, total_out, stream);
+}
+
 int gk_group_passes(int64_t S) {
   int bits = 0;
   while (bits < 31 && ((int64_t)1 << bits) < S) ++bits;  // bits of S - 1

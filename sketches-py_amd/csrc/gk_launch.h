@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "gk_dirhash.h"
 #include "gk_state.h"
 
 // Capacity of the fast LDS class (every stream starts there when P <= 128).
@@ -271,6 +272,46 @@ inline int64_t gk_group_sums(int64_t count) {
 // id >= S leaves its outputs alone, except that out_offsets becomes all zero.
 hipError_t gk_launch_group_by_key(const GKGroupScratch& sc, const int32_t* ids, const double* values, int64_t count,
                                   int64_t S, double* out_values, int64_t* out_offsets, hipStream_t stream);
+// ---- key directory (gk_dir.hip): int64 keys -> int32 ids, a device hash table ----
+// Exclusive scan in place of n uint32 values whose sum stays below 2^32 (the
+// same k_scan_* kernels); *total_out (device, may be NULL) = the sum.  skip
+// (device, may be NULL): a non-zero word makes the scan do nothing.
+hipError_t gk_launch_scan_u32(uint32_t* a, int64_t n, unsigned long long* sums, const unsigned long long* skip,
+                              unsigned long long* total_out, hipStream_t stream);
+struct GKDirTable {
+  unsigned long long* keys;  // [T] GK_DIR_NONE = empty
+  uint2* meta;               // [T] x: id (0xFFFFFFFF unassigned), y: first-occurrence word
+  int64_t* key_of_id;        // [capacity]
+  uint32_t T;                // slots, a power of two (gk_dir_slots)
+  int64_t capacity;
+  GKDirHome home;
+};
+#define GK_DIR_NO_FIRST 0xFFFFFFFFu    // idle first-occurrence word (sample indices are < 2^31)
+#define GK_DIR_SLOT_NONE 0xFFFFFFFFu   // slot_of: GK_DIR_NONE sample / unknown key
+#define GK_DIR_SLOT_FULL 0xFFFFFFFEu   // slot_of: the probe ran out of slots
+// Control words of a directory call (zeroed by the caller, but for the last):
+#define GK_DIR_CTL_OVF 0    // the table or the id space ran out
+#define GK_DIR_CTL_NEW 1    // the scan's total: keys added by this call
+#define GK_DIR_CTL_NONE 2   // count minus the first index of a GK_DIR_NONE key (as GK_SEL_FIRST)
+#define GK_DIR_CTL_DUP 3    // import: count minus the first index of a repeated key
+#define GK_DIR_CTL_IDLE 4   // SET by the caller, cleared by k_dir_insert on meeting a slot without an id:
+                            //   while set, k_dir_flag, the scan and k_dir_number (assign) return at once
+#define GK_DIR_CTL_WORDS 5
+// every slot empty, unassigned and idle
+hipError_t gk_launch_dir_clear(const GKDirTable& t, hipStream_t stream);
+// slot_of[i] = the slot of keys[i], claimed if the key is new; first-occurrence words of unassigned slots
+hipError_t gk_launch_dir_insert(const GKDirTable& t, const int64_t* keys, int64_t count, uint32_t* slot_of,
+                                unsigned long long* ctl, hipStream_t stream);
+// flag[i] = sample i is the first occurrence of a key without an id
+hipError_t gk_launch_dir_flag(const GKDirTable& t, const uint32_t* slot_of, int64_t count, uint32_t* flag,
+                              const unsigned long long* ctl, hipStream_t stream);
+// first occurrences take id = size + rank[i] (rank NULL: id = i, and any other sample is a repeat)
+hipError_t gk_launch_dir_number(const GKDirTable& t, const int64_t* keys, const uint32_t* slot_of,
+                                const uint32_t* rank, int64_t count, int64_t size, unsigned long long* ctl,
+                                hipStream_t stream);
+// out_ids[i] = id of slot_of[i], or (slot_of NULL) of keys[i] by a read-only probe; -1 if none
+hipError_t gk_launch_dir_lookup(const GKDirTable& t, const int64_t* keys, const uint32_t* slot_of, int64_t count,
+                                int32_t* out_ids, hipStream_t stream);
 // every stream back to an empty sketch in class 0; ctr: also zero the set's
 // counter words [0, GK_CTR_FATAL) (slots used, member-list lengths) and the
 // per-call block [GK_CTR_CALL, GK_CALL_BYTES) (what begin_call's memset zeroes)

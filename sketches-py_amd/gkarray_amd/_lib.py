@@ -83,6 +83,14 @@ SYMBOLS = {
     "gk_unpack_select": (_INT, [_P, _P, _I64, _P, _P]),
     "gk_peek": (_INT, [ctypes.c_char_p, ctypes.POINTER(_D), ctypes.POINTER(_I64)]),
     "gk_load": (_INT, [_P, ctypes.c_char_p, _P]),
+    "gk_dir_create": (_INT, [_I64, _INT, ctypes.POINTER(_P)]),
+    "gk_dir_destroy": (_INT, [_P]),
+    "gk_dir_capacity": (_I64, [_P]),
+    "gk_dir_size": (_I64, [_P]),
+    "gk_dir_assign": (_INT, [_P, _P, _I64, _P, ctypes.POINTER(_I64), _P]),
+    "gk_dir_lookup": (_INT, [_P, _P, _I64, _P, _P]),
+    "gk_dir_keys": (_INT, [_P, _P, _P]),
+    "gk_dir_import": (_INT, [_P, _P, _I64, _P]),
     "gk_num_streams": (_I64, [_P]),
     "gk_eps": (_D, [_P]),
     "gk_flush_period": (_INT, [_P]),
