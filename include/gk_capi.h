@@ -80,7 +80,11 @@ int gk_create(int64_t num_streams, double eps, int64_t cap_hint, int device,
               gk_set** out);
 int gk_destroy(gk_set* set);
 
-/* Reset every stream to the freshly constructed state (gk:21-29). */
+/* Reset every stream to the freshly constructed state (gk:21-29).  Does not
+ * wait for the set's last call: streams that call deferred are not re-run,
+ * their state being void -- unless that call carried a fused query and has not
+ * been settled yet (by gk_sync or any later call): the re-run writes those
+ * streams' rows of the query's output, so it is settled first. */
 int gk_reset(gk_set* set, void* stream);
 
 /* Batched GKArray.add (gk:49-61): stream s receives, in order,

@@ -413,7 +413,11 @@ int replay_deferred(gk_set* h, hipStream_t s) {
 int settle(gk_set* h, hipStream_t s, bool block) {
   poll(h, block || h->last.may_defer);
   if (h->done_pending) return GK_OK;  // still running, and it cannot have deferred anything
-  return replay_deferred(h, s);
+  const int rc = replay_deferred(h, s);
+  // settled: nothing is re-run from that call any more, so its fused query is
+  // forgotten (gk_reset waits only for a query whose call is not settled yet)
+  if (!rc) h->last.q = GKQuery();
+  return rc;
 }
 
 // Before a call: keep every class's arena at least twice what is in use, so
@@ -1137,6 +1141,15 @@ int gk_reset(gk_set* h, void* stream) {
   // critical path: ~90 us of idle GPU per step, 10 % of a 125k-stream rank
   // share.)  The last call's counters are consumed when they arrive: its
   // sticky errors are still reported, its deferred list is dropped.
+  // The exception is a call with a fused query (gk_ingest_quantiles,
+  // gk_ingest_keyed with qs): the answers of a stream it deferred are written
+  // by the re-run alone, so that call is settled first, as before any other
+  // call.  (A plain gk_ingest, the rank share's step, never takes this wait,
+  // nor does a fused-query call that a later call or gk_sync has settled.)
+  if (h->last.q.out && h->last.may_defer) {
+    rc = settle(h, s, false);
+    if (rc) return rc;
+  }
   poll(h, false);
   if (h->done_pending) h->void_defer = true;
   else h->h_ctr[GK_CTR_DEFER] = 0;

@@ -4655,6 +4655,42 @@ __device__ __forceinline__ int merge_convert(const MergeLDS& m, const GKRec* __r
     }
     base += __popcll(bal);
   }
+  // The list above is sorted by value while other._min <= v_0.  A table whose
+  // first value lies below _min (explicit records below the minimum,
+  // gk_merge_compress) leaves the first record out of place: the stable sort
+  // of gk:72 moves it behind the records of smaller values, ahead of equal
+  // ones.  Those form a prefix of records 1.. (the table is sorted).
+  if (oE > 0 && omn > otab[0].v && (int64_t)otab[0].g + otab[0].d - spread - 1 > 0 && base > 1) {  // (wave-uniform)
+    __syncthreads();
+    int cnt = 0;
+    for (int i0 = 1; i0 < base; i0 += 64) {
+      const int i = i0 + lane;
+      cnt += __popcll(__ballot(i < base && m.rv[i] < omn));
+    }
+    if (cnt > 0) {
+      const int32_t g0 = m.rg[0];
+      for (int i0 = 0; i0 < cnt; i0 += 64) {
+        const int i = i0 + lane;
+        double v1 = 0.0;
+        int32_t g1 = 0;
+        if (i < cnt) {
+          v1 = m.rv[i + 1];
+          g1 = m.rg[i + 1];
+        }
+        __syncthreads();
+        if (i < cnt) {
+          m.rv[i] = v1;
+          m.rg[i] = g1;
+        }
+        __syncthreads();
+      }
+      if (lane == 0) {
+        m.rv[cnt] = omn;
+        m.rg[cnt] = g0;
+      }
+      __syncthreads();
+    }
+  }
   return base;
 }
 

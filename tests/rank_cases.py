@@ -77,11 +77,13 @@ def same_i64(got, exp, what):
                              % (what, len(bad), r, c, got[r, c], exp[r, c]))
 
 
-def check_ranks(ss, oracles, ids, xs, what, lo=True, hi=True):
+def check_ranks(ss, oracles, ids, xs, what, lo=True, hi=True, before=True):
     """ranks (ids None) / ranks_select on the engine against expected_ranks on
-    the covered oracles; then every stream's state.  Returns the engine's pair."""
+    the covered oracles; then every stream's state.  Returns the engine's pair.
+    `before` as in select_cases.check_query."""
     covered = list(range(len(oracles))) if ids is None else list(ids)
-    before = R.snapshot(ss)
+    if before is True:
+        before = R.snapshot(ss)
     flush_covered(oracles, covered)
     elo, ehi = expected_rows(oracles, covered, xs)
     if ids is None:

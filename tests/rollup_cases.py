@@ -480,3 +480,52 @@ def case_overflow(dev, member):
     assert ei.value.code == GK_E_OVERFLOW, ei.value
     assert_set_matches(dst, dst_o, "after GK_E_OVERFLOW: dst")
     assert_set_matches(src, src_o, "after GK_E_OVERFLOW: src")
+
+
+def case_merge_source_with_records_below_min(dev):
+    """Found by the random sequences of opseq_cases (moves through the host
+    engine, eps = 0.01, seed 1004, step 10): merge_compress(entries) gave a
+    source stream records below its _min, so that its table starts below
+    other._min and the converted list (other._min, ...), (v_0, ...), ... of
+    gk:136-147 is not sorted as it stands; gk:72 sorts it.  Sources: a 1-value
+    stream with 11 records around its value (the sequence's own), one with 70
+    records below _min (more than a wave of records move), one with records
+    equal to _min (the sort is stable: _min's record stays ahead of them), and
+    an untouched one.  Both folds: merge_from and rollup_from."""
+    eps = 0.01
+    for fold in ("merge", "rollup"):
+        src_vals = [np.asarray([1.3505]), np.asarray([100.0, 101.0]), np.asarray([5.0, 6.0, 7.0]), seq(1, 150, 861)]
+        recs = [[(0.2489, 1, 1), (0.9105, 3, 5), (1.0683, 4, 2), (1.3505, 4, 5), (1.3505, 3, 3), (1.3505, 2, 0),
+                 (1.3505, 1, 5), (1.3505, 3, 0), (1.4288, 3, 5), (1.5422, 4, 1), (1.5982, 2, 0)],
+                [(float(k), 1 + k % 3, k % 4) for k in range(70)],
+                [(5.0, 2, 1), (5.0, 1, 3), (5.5, 2, 0)],
+                []]
+        dspecs = [(7, 10, 862), (1, 57, 863), (0, 0, 864), (2, 250, 865)]
+        src = U._ss(len(src_vals), eps, dev)
+        U.ingest_np(src, src_vals)
+        src_o = []
+        for x in src_vals:
+            o = OracleGK(eps)
+            o.add_many(x)
+            src_o.append(o)
+        flat = [r for rs in recs for r in rs]
+        offs = np.concatenate([[0], np.cumsum([len(rs) for rs in recs])]).astype(np.int64)
+        src.merge_compress(torch.tensor([r[0] for r in flat], dtype=torch.float64),
+                           torch.tensor([r[1] for r in flat], dtype=torch.int32),
+                           torch.tensor([r[2] for r in flat], dtype=torch.int32), torch.from_numpy(offs))
+        for o, rs in zip(src_o, recs):
+            o.flush(rs)
+        assert all(o.v[0] < o.min for o in src_o[:2]) and src_o[2].v[0] == src_o[2].min
+        assert_set_matches(src, src_o, "records below _min: src")
+        dst = make_set(dev, eps, dspecs)
+        dst_o = [oracle_of(eps, sp) for sp in dspecs]
+        groups = [[0], [1], [2], [3]]
+        if fold == "merge":
+            dst.merge_from([src])
+            oracle_fold(dst_o, src_o, groups)
+            assert_set_matches(dst, dst_o, "records below _min, merge_from: dst")
+            assert_set_matches(src, src_o, "records below _min, merge_from: src")
+        else:
+            check_rollup(dst, src, dst_o, src_o, [[1, 0], [2], [], [3]], "records below _min, rollup", quantiles=False)
+        assert all(dst_o[j].v == sorted(dst_o[j].v) for j in range(4))
+        assert_quantiles(dst, dst_o, "records below _min, %s" % fold)

@@ -76,9 +76,13 @@ def oracle_answers(oracles, ids, qs, single):
     return np.asarray(rows, dtype=np.float64).reshape(len(ids), len(qs))
 
 
-def check_query(ss, oracles, ids, qs, single, what):
-    """quantiles_select on the engine, quantile()/quantiles() on the listed oracles only."""
-    before = R.snapshot(ss)
+def check_query(ss, oracles, ids, qs, single, what, before=True):
+    """quantiles_select on the engine, quantile()/quantiles() on the listed oracles only.
+    `before`: True takes the snapshot that unlisted streams are compared with; a
+    snapshot the caller holds is used as it is; None makes quantiles_select the
+    first call the set sees (no comparison with the state before)."""
+    if before is True:
+        before = R.snapshot(ss)
     got = ss.quantiles_select(i32(ids), qs, single=single).cpu().numpy()
     assert got.shape == (len(ids), len(qs))
     U.assert_same_quantiles(got, oracle_answers(oracles, ids, qs, single), what + " answers", None)
@@ -323,3 +327,33 @@ def case_deferred(dev):
     U.assert_same_quantiles(got, oracle_answers(orc, ids, Q3, False), "deferred answers", None)
     assert ss.num_promoted > 2  # more streams than the 2 slots a class started with: some were deferred
     assert_all(ss, orc, "deferred")
+
+
+# ------------- case 9: a fused query left in flight, then reset() (found by the
+# random sequences of opseq_cases: tiny arenas, eps = 0.01, seed 23, step 104)
+def case_reset_after_fused_query_in_flight(dev):
+    """(GK_POOL_SLOTS=2 set by the caller) ``ingest(quantiles=..., sync=False)``
+    defers most of its overflowing streams, and ``reset()`` follows directly.
+    The reset voids the streams' state, not the answers of the call before it:
+    every row of the fused query's output is the oracle's, the deferred streams'
+    rows included, which only the re-run writes."""
+    specs = [("D", 600 + 75 * k, 0) if k % 4 else (k % 8, 150 + 50 * k, 960 + k) for k in range(14)]
+    S = len(specs)
+    ss = U._ss(S, EPS, dev)
+    flat, offs = U.csr([seq(sp) for sp in specs])
+    tf, to = torch.from_numpy(flat).to(dev), torch.from_numpy(offs).to(dev)
+    # (the output is allocated uninitialised: leave a block of that size behind that holds no answer)
+    junk = torch.full((S, len(Q3)), -7.0, dtype=torch.float64, device=tf.device)
+    del junk
+    got = ss.ingest(tf, to, quantiles=Q3, sync=False)
+    ss.reset()
+    ss.sync()
+    orc = [oracle_of(EPS, sp) for sp in specs]
+    U.assert_same_quantiles(got.cpu().numpy(), oracle_answers(orc, range(S), Q3, False),
+                            "answers of the call before reset()", None)
+    fresh = [OracleGK(EPS) for _ in range(S)]
+    assert_all(ss, fresh, "after reset()")
+    # and the set starts over: the same batch again, settled by a selection
+    ss.ingest(tf, to, sync=False)
+    again = [oracle_of(EPS, sp) for sp in specs]
+    check_query(ss, again, [13, 1, 4, 2, 9, 1], Q3, False, "the same batch after reset()")

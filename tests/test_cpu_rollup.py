@@ -25,6 +25,10 @@ def test_cpu_merge_and_merge_compress_ladder_case():
     C.case_merge_ladder("cpu")
 
 
+def test_cpu_merge_of_source_with_records_below_min():
+    C.case_merge_source_with_records_below_min("cpu")
+
+
 def test_cpu_rollup_equals_merge_from():
     C.case_equivalence("cpu")
 

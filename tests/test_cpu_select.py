@@ -37,6 +37,10 @@ def test_cpu_select_errors_leave_state():
     C.case_errors("cpu")
 
 
+def test_cpu_select_reset_after_fused_query_in_flight():
+    C.case_reset_after_fused_query_in_flight("cpu")
+
+
 def test_select_symbols_are_bound():
     from gkarray_amd import _lib
     for name in ("gk_quantiles_select", "gk_flush_select", "gk_reset_select", "gk_stats_select"):

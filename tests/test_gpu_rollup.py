@@ -36,6 +36,12 @@ def test_merge_and_merge_compress_climb_narrow_ladder(gpu_device, monkeypatch):
     C.case_merge_ladder(gpu_device)
 
 
+def test_merge_of_source_with_records_below_min(gpu_device):
+    """merge_from and rollup_from of source streams whose tables start below
+    their _min (records from merge_compress): the converted list is sorted (gk:72)."""
+    C.case_merge_source_with_records_below_min(gpu_device)
+
+
 def test_merge_and_merge_compress_overflow_keep_state(gpu_device, monkeypatch):
     """GK_E_OVERFLOW of merge_from and merge_compress(entries) on the ladder
     128,200: the stream that did not fit is bit-identical to before the call

@@ -58,3 +58,10 @@ def test_select_settles_deferred_streams_first(gpu_device, monkeypatch):
     re-run before the selection reads them."""
     monkeypatch.setenv("GK_POOL_SLOTS", "2")
     C.case_deferred(gpu_device)
+
+
+def test_select_reset_after_fused_query_in_flight(gpu_device, monkeypatch):
+    """Case 9: with 2-slot arenas, reset() directly after an ingest with a
+    fused query left in flight: the deferred streams' answers are still written."""
+    monkeypatch.setenv("GK_POOL_SLOTS", "2")
+    C.case_reset_after_fused_query_in_flight(gpu_device)
