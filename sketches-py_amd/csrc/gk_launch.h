@@ -1,4 +1,4 @@
-// gk_launch.h -- host-side launchers of the HIP kernels (gk_kernels.hip),
+// gk_launch.h -- host-side launchers of the HIP kernels (the gk_*.hip units),
 // used by the C ABI runtime (gk_capi.cpp).
 #pragma once
 #include <hip/hip_runtime.h>

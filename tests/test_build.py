@@ -1,8 +1,9 @@
 """Build-level invariants of the HIP kernels (no GPU needed: hipcc
 cross-compiles for gfx950 here)."""
+import glob
+import importlib.util
 import os
 import re
-import subprocess
 
 import pytest
 
@@ -11,38 +12,32 @@ CSRC = os.path.join(ROOT, "sketches-py_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
-def resource_report(tmp_path_factory):
-    out = tmp_path_factory.mktemp("res") / "k.o"
-    r = subprocess.run(
-        ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-         "-Wno-unused-result", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
-         "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, "gk_kernels.hip"), "-o", str(out)],
-        capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kernels = {}
-    cur = None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            kernels[cur] = {}
-            continue
-        m = re.search(r"remark:\s+(.+?): (\d+) \[", line)
-        if cur and m:
-            kernels[cur][m.group(1).strip()] = int(m.group(2))
-    return kernels
+def units():
+    """Every unit of csrc compiled once, with the Makefile's flags, by
+    tools/isa_diff.py: {unit: (device assembly, resource remarks)} and the
+    module itself."""
+    spec = importlib.util.spec_from_file_location("isa_diff", os.path.join(ROOT, "tools", "isa_diff.py"))
+    isa_diff = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(isa_diff)
+    return isa_diff, isa_diff.compile_tree(ROOT)
 
 
 @pytest.fixture(scope="module")
-def small_isa(tmp_path_factory):
-    out = tmp_path_factory.mktemp("isa") / "k.s"
-    r = subprocess.run(
-        ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-         "-Wno-unused-result", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "--cuda-device-only", "-S",
-         os.path.join(CSRC, "gk_kernels.hip"), "-o", str(out)],
-        capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    text = open(out).read()
+def small_unit(units):
+    """(assembly, remarks) of the unit that holds k_ingest_small."""
+    small = [u for u in units[1].values() if any(n.startswith("_Z14k_ingest_small") for n in u[1])]
+    assert len(small) == 1
+    return small[0]
+
+
+@pytest.fixture(scope="module")
+def resource_report(small_unit):
+    return {k: {n: int(x) for n, x in v.items() if x.isdigit()} for k, v in small_unit[1].items()}
+
+
+@pytest.fixture(scope="module")
+def small_isa(small_unit):
+    text = small_unit[0]
     bodies = {}
     for m in re.finditer(r"^(_Z14k_ingest_small\w+):", text, re.M):
         end = text.index("s_endpgm", m.end())
@@ -84,10 +79,30 @@ def test_fast_class_has_no_scratch(resource_report, small_isa):
 def test_no_inline_asm_memory_ops():
     """Inline-asm loads were rejected: the compiler may copy an asm output
     register before the load lands (tools/check_async_loads.py found such
-    copies).  Memory operations in the kernels stay compiler-visible."""
-    src = open(os.path.join(CSRC, "gk_kernels.hip")).read()
-    for m in re.finditer(r'asm\s+volatile\s*\(\s*"([^"]*)"', src):
-        assert "load" not in m.group(1) and "store" not in m.group(1), m.group(1)
+    copies).  Memory operations in the kernels stay compiler-visible: in
+    every kernel unit and every header of csrc."""
+    files = sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.h")))
+    assert os.path.join(CSRC, "gk_ops.hip") in files and os.path.join(CSRC, "gk_dev.h") in files
+    for f in files:
+        for m in re.finditer(r'asm\s+volatile\s*\(\s*"([^"]*)"', open(f).read()):
+            assert "load" not in m.group(1) and "store" not in m.group(1), (f, m.group(1))
+
+
+def test_every_kernel_lives_in_one_unit(units):
+    """The library is linked without relocatable device code: a kernel or a
+    noinline device function that two units define would be two copies.
+    Every unit of csrc compiles for gfx950 with the Makefile's flags, and no
+    function name comes out of two of them."""
+    isa_diff, compiled = units
+    assert set(compiled) == {os.path.basename(f) for f in glob.glob(os.path.join(CSRC, "*.hip"))}
+    where, remarks = {}, []
+    for unit, (text, res) in compiled.items():
+        for n in isa_diff.functions(text):
+            assert n not in where, (n, where[n], unit)
+            where[n] = unit
+        remarks += list(res)
+    assert len(set(remarks)) == len(remarks) >= 48, len(remarks)
+    assert set(remarks) <= set(where)
 
 
 def test_fast_class_occupancy(resource_report):
