@@ -475,8 +475,14 @@ int gk_unpack_select(gk_set* set, const int32_t* ids, int64_t count, const void*
  * looks up or inserts a whole batch of sample keys in one call.  Its ids are
  * what gk_ingest_keyed, the gk_*_select calls, gk_pack_select and roll-up
  * member lists take.  A directory is an object of its own, not part of a
- * set: one directory may serve several sets.  It is insert-only; the caller
- * compacts the id space with gk_dir_keys -> filter -> gk_dir_import.
+ * set: one directory may serve several sets.  Keys can be removed
+ * (gk_dir_remove); the ids they held are handed out again, smallest first.
+ *  - State.  Besides its keys a directory holds `bound`, one past the
+ *    largest id handed out since the last import (gk_dir_bound), and `free`,
+ *    the ids below `bound` that no key holds.  len(d) (gk_dir_size) is the
+ *    number of keys held; always len(d) + |free| == bound <= capacity.  With
+ *    no removal `free` is empty and bound == len(d).  The id space only
+ *    shrinks by gk_dir_keys -> filter -> gk_dir_import.
  *  - Memory.  `keys` (int64), `out_ids` (int32) and `out_keys` (int64) are
  *    device memory on the directory's GPU for the GPU engine, host memory
  *    for the CPU engine.  `num_new` is host memory.
@@ -484,8 +490,9 @@ int gk_unpack_select(gk_set* set, const int32_t* ids, int64_t count, const void*
  *    valid with NULL arrays; a NULL array with count > 0 is GK_E_ARG.
  *  - GK_DIR_NONE is "no key": it is never stored and always answers id -1,
  *    gk_ingest_keyed's "not for this set".  Every other int64 value is a key.
- *  - Synchronisation.  gk_dir_assign, gk_dir_lookup, gk_dir_keys and
- *    gk_dir_import synchronise before returning.  A directory is not
+ *  - Synchronisation.  gk_dir_assign, gk_dir_remove, gk_dir_lookup,
+ *    gk_dir_keys, gk_dir_import and gk_dir_import_sparse synchronise before
+ *    returning.  A directory is not
  *    thread-safe; its calls must be ordered on one stream.
  *
  * gk_dir_create: an empty directory of at most `capacity` keys, 1 <= capacity
@@ -495,38 +502,65 @@ int gk_unpack_select(gk_set* set, const int32_t* ids, int64_t count, const void*
  *           k = keys[i]
  *           if k == GK_DIR_NONE:   out_ids[i] = -1
  *           elif k in d:           out_ids[i] = d[k]
- *           else:                  d[k] = len(d); out_ids[i] = d[k]
- *   New keys are numbered in order of FIRST OCCURRENCE in the batch,
- *   continuing from gk_dir_size: every output is a function of the
- *   directory's history and the batch alone -- not of the hash, the probe
- *   order or the scheduling of the device's threads -- and the two engines
- *   give identical ids.  *num_new (may be NULL) receives the number of keys
- *   added.  GK_E_OVERFLOW if len(d) would pass `capacity`: the call is then
- *   void and the directory exactly as before it (gk_dir_size, gk_dir_keys and
- *   every later gk_dir_lookup / gk_dir_assign answer as if it had not
- *   happened); out_ids is unspecified and *num_new is not written.
+ *           elif free:             d[k] = min(free); free.remove(d[k]); out_ids[i] = d[k]
+ *           else:                  d[k] = bound; bound += 1; out_ids[i] = d[k]
+ *   The r-th new key of the batch, in order of FIRST OCCURRENCE, gets the
+ *   r-th smallest id that was free when the call began and, once those run
+ *   out, bound, bound + 1, ...: every output is a function of the directory's
+ *   contents and the batch alone -- not of which gk_dir_remove freed an id or
+ *   in what order, nor of the hash, the probe order or the scheduling of the
+ *   device's threads -- and the two engines give identical ids.  A removed
+ *   key that comes back is a new key: it takes the smallest free id, which
+ *   need not be its old one.  *num_new (may be NULL) receives the number of
+ *   keys added.  GK_E_OVERFLOW exactly when len(d) + new keys > capacity: the
+ *   call is then void and the directory exactly as before it (gk_dir_size,
+ *   gk_dir_bound, the free ids, gk_dir_keys and every later answer are as if
+ *   it had not happened); out_ids is unspecified and *num_new is not written.
+ * gk_dir_remove is this loop:
+ *       for i in 0 .. count-1:
+ *           k = keys[i]
+ *           if k == GK_DIR_NONE or k not in d:  out_ids[i] = -1
+ *           else:  out_ids[i] = d.pop(k); free.add(out_ids[i])
+ *   A key listed twice is removed by its first occurrence; the later ones
+ *   answer -1.  *num_removed (may be NULL) receives the number of keys
+ *   removed.  "Not found" is an answer, never an error.  out_ids is required
+ *   when count > 0.  The directory does not touch any set: the caller must
+ *   reset the stream of a removed id (gk_reset_select) before a new key
+ *   inherits it.
  * gk_dir_lookup: read-only; out_ids[i] = d[keys[i]], or -1 for a key the
  *   directory does not hold and for GK_DIR_NONE.
- * gk_dir_keys: the inverse array, out_keys[id] = the key that holds id, for
- *   id in [0, gk_dir_size); out_keys may be NULL while the directory is empty.
+ * gk_dir_bound: one past the largest id handed out; -1 for NULL.
+ * gk_dir_keys: the inverse array, out_keys[id] = the key that holds id, or
+ *   GK_DIR_NONE for a free id, for id in [0, gk_dir_bound); out_keys may be
+ *   NULL while gk_dir_bound is 0.
  * gk_dir_import: replaces the contents with keys[i] -> i, i in [0, count)
- *   (restore, a copy of another capacity, a compacted id space).  GK_E_ARG for
+ *   (restore, a copy of another capacity, a compacted id space); afterwards
+ *   bound == size == count and no id is free.  GK_E_ARG for
  *   count > capacity, for a GK_DIR_NONE entry (its first index in the
  *   message) and for a key listed twice (the first index that repeats an
  *   earlier entry, and the key, in the message): refused BEFORE anything is
  *   mutated -- the new contents are built in a second table that replaces the
  *   first on success.
+ * gk_dir_import_sparse: gk_dir_import, except that a GK_DIR_NONE entry is a
+ *   free id: keys[i] -> i for the other entries and bound = count (what
+ *   gk_dir_keys wrote for a directory with free ids; restore and copies of
+ *   such a directory).  The other two refusals are gk_dir_import's.
  *  - Memory (per capacity).  The table has T slots, T the power of two >=
  *    2 * capacity and at least 64; a slot holds an 8-byte key, a 4-byte id and
  *    a 4-byte first-occurrence word (16 T bytes); the inverse array adds 8
- *    bytes per id of `capacity`.  gk_dir_import holds two tables while it
- *    runs.  GK_E_NOMEM is returned before anything is mutated.
+ *    bytes per id of `capacity` and the list of free ids 4 bytes per id of
+ *    `capacity`.  A removed key keeps its slot until the table is rebuilt
+ *    from the inverse array, which gk_dir_remove does once removals since
+ *    the last rebuild pass T/4 slots (on the stream, no second table).  The
+ *    imports hold two tables while they run.  GK_E_NOMEM is returned before
+ *    anything is mutated.
  *  - Scratch (GPU engine; owned by the directory, only grows, freed by
- *    gk_dir_destroy).  gk_dir_assign and gk_dir_import: 8 bytes per sample
- *    (the sample's slot and its first-occurrence flag, scanned in place into
- *    its rank) + 8 bytes per 2048 samples (the scan's tile sums), sized for
- *    max(count, gk_dir_size) samples so that a void call can always rebuild
- *    the table.  gk_dir_lookup and gk_dir_keys need none.
+ *    gk_dir_destroy).  gk_dir_assign, gk_dir_remove and the imports: 8 bytes
+ *    per sample (the sample's slot and its first-occurrence flag, scanned in
+ *    place into its rank) + 8 bytes per 2048 samples (the scan's tile sums),
+ *    sized for max(count, gk_dir_bound) samples so that a void call can
+ *    always rebuild the table and a remove the list of free ids.
+ *    gk_dir_lookup and gk_dir_keys need none.
  *  - GK_DIR_HASH_BITS=b (environment, read by gk_dir_create; tests) confines
  *    the keys' home slots to the last 2^b slots of the table: b = 0 makes the
  *    table one probe chain that wraps round its end.  Not a number >= 0:
@@ -536,12 +570,16 @@ typedef struct gk_dir gk_dir;
 int gk_dir_create(int64_t capacity, int device, gk_dir** out);
 int gk_dir_destroy(gk_dir* dir);
 int64_t gk_dir_capacity(const gk_dir* dir);
-int64_t gk_dir_size(const gk_dir* dir);  /* keys assigned so far */
+int64_t gk_dir_size(const gk_dir* dir);  /* keys held */
+int64_t gk_dir_bound(const gk_dir* dir); /* one past the largest id handed out */
 int gk_dir_assign(gk_dir* dir, const int64_t* keys, int64_t count, int32_t* out_ids, int64_t* num_new,
+                  void* stream);
+int gk_dir_remove(gk_dir* dir, const int64_t* keys, int64_t count, int32_t* out_ids, int64_t* num_removed,
                   void* stream);
 int gk_dir_lookup(gk_dir* dir, const int64_t* keys, int64_t count, int32_t* out_ids, void* stream);
 int gk_dir_keys(gk_dir* dir, int64_t* out_keys, void* stream);
 int gk_dir_import(gk_dir* dir, const int64_t* keys, int64_t count, void* stream);
+int gk_dir_import_sparse(gk_dir* dir, const int64_t* keys, int64_t count, void* stream);
 
 /* Introspection for tests and benchmarks. */
 int64_t gk_num_streams(const gk_set* set);

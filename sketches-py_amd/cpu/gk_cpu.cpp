@@ -20,6 +20,7 @@
 #include <atomic>
 #include <chrono>
 #include <limits>
+#include <set>
 #include <string>
 #include <thread>
 
@@ -1118,11 +1119,15 @@ int gk_unpack_select(gk_set* h, const int32_t* ids, int64_t count, const void* b
 
 namespace {
 // linear probing over T slots (gk_dirhash.h: geometry, hash and the
-// GK_DIR_HASH_BITS switch are the device engine's)
+// GK_DIR_HASH_BITS switch are the device engine's).  A removed key stays in
+// its slot with id -1, its own tombstone: probes walk over it, and the key
+// finds the slot again when it comes back.
 struct DirTable {
   std::vector<int64_t> keys;  // GK_DIR_NONE = empty
-  std::vector<int32_t> ids;
-  std::vector<int64_t> key_of_id;
+  std::vector<int32_t> ids;   // -1: empty slot, or a removed key's
+  std::vector<int64_t> key_of_id;  // [0, bound): GK_DIR_NONE at free ids
+  std::set<int32_t> free;          // the ids below bound that no key holds
+  int64_t dead = 0;                // upper bound on slots that hold a removed key
   uint32_t T = 0;
   GKDirHome home = {};
 
@@ -1131,7 +1136,11 @@ struct DirTable {
     keys.assign((size_t)slots, GK_DIR_NONE);
     ids.assign((size_t)slots, -1);
     key_of_id.clear();
+    free.clear();
+    dead = 0;
   }
+  int64_t bound() const { return (int64_t)key_of_id.size(); }
+  int64_t size() const { return bound() - (int64_t)free.size(); }
   // the slot of k, or the empty slot where its probe ends (T full slots: -1)
   int64_t find(int64_t k) const {
     uint32_t slot = gk_dir_home(home, gk_dir_mix((uint64_t)k));
@@ -1141,11 +1150,30 @@ struct DirTable {
     }
     return -1;
   }
-  // d[k] = len(d) for a key the table does not hold (slot: find's answer)
-  void add(int64_t slot, int64_t k) {
+  bool holds(int64_t slot, int64_t k) const {
+    return slot >= 0 && keys[(size_t)slot] == k && ids[(size_t)slot] >= 0;
+  }
+  // d[k] = id for a key the table does not hold (slot: find's answer; id: a hole of key_of_id or its end)
+  void bind(int64_t slot, int64_t k, int32_t id) {
     keys[(size_t)slot] = k;
-    ids[(size_t)slot] = (int32_t)key_of_id.size();
-    key_of_id.push_back(k);
+    ids[(size_t)slot] = id;
+    if ((int64_t)id == bound())
+      key_of_id.push_back(k);
+    else
+      key_of_id[(size_t)id] = k;
+  }
+  // every slot again from key_of_id (free ids skipped): no tombstones, no slots of a void call
+  void rebuild() {
+    keys.assign((size_t)T, GK_DIR_NONE);
+    ids.assign((size_t)T, -1);
+    for (int64_t id = 0; id < bound(); ++id) {
+      const int64_t k = key_of_id[(size_t)id];
+      if (k == GK_DIR_NONE) continue;
+      const int64_t slot = find(k);
+      keys[(size_t)slot] = k;
+      ids[(size_t)slot] = (int32_t)id;
+    }
+    dead = 0;
   }
 };
 }  // namespace
@@ -1154,6 +1182,37 @@ struct gk_dir {
   int64_t capacity = 0;
   DirTable t;
 };
+
+namespace {
+// gk_dir_import (sparse false: a GK_DIR_NONE entry is refused) and gk_dir_import_sparse
+int dir_import(gk_dir* d, const int64_t* keys, int64_t count, bool sparse) {
+  if (count > d->capacity) return fail_dir_import_count(count, d->capacity);
+  if (!sparse)
+    for (int64_t i = 0; i < count; ++i)
+      if (keys[i] == GK_DIR_NONE) return fail_dir_import_none(i);
+  // built in a second table that replaces the first on success
+  DirTable nt;
+  nt.home = d->t.home;
+  try {
+    nt.clear(d->t.T);
+    nt.key_of_id.reserve((size_t)count);
+  } catch (...) {
+    return fail(GK_E_NOMEM, "directory: no memory for a second table");
+  }
+  for (int64_t i = 0; i < count; ++i) {
+    if (keys[i] == GK_DIR_NONE) {
+      nt.key_of_id.push_back(GK_DIR_NONE);
+      nt.free.insert((int32_t)i);
+      continue;
+    }
+    const int64_t slot = nt.find(keys[i]);
+    if (nt.keys[(size_t)slot] == keys[i]) return fail_dir_import_repeat(i, keys[i]);
+    nt.bind(slot, keys[i], (int32_t)i);
+  }
+  d->t = std::move(nt);
+  return GK_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -1183,14 +1242,16 @@ int gk_dir_destroy(gk_dir* d) {
 }
 
 int64_t gk_dir_capacity(const gk_dir* d) { return d ? d->capacity : -1; }
-int64_t gk_dir_size(const gk_dir* d) { return d ? (int64_t)d->t.key_of_id.size() : -1; }
+int64_t gk_dir_size(const gk_dir* d) { return d ? d->t.size() : -1; }
+int64_t gk_dir_bound(const gk_dir* d) { return d ? d->t.bound() : -1; }
 
 int gk_dir_assign(gk_dir* d, const int64_t* keys, int64_t count, int32_t* out_ids, int64_t* num_new, void* stream) {
   (void)stream;
   int rc = check_dir_args(d, keys, count, out_ids, true);
   if (rc) return rc;
   DirTable& t = d->t;
-  const int64_t size0 = (int64_t)t.key_of_id.size();
+  const int64_t bound0 = t.bound(), size0 = t.size();
+  std::vector<int32_t> fresh;  // the ids this call has handed out, to take back if it turns out void
   for (int64_t i = 0; i < count; ++i) {
     const int64_t k = keys[i];
     if (k == GK_DIR_NONE) {
@@ -1198,21 +1259,61 @@ int gk_dir_assign(gk_dir* d, const int64_t* keys, int64_t count, int32_t* out_id
       continue;
     }
     const int64_t slot = t.find(k);
-    if (slot >= 0 && t.keys[(size_t)slot] == k) {
+    if (t.holds(slot, k)) {
       out_ids[i] = t.ids[(size_t)slot];
       continue;
     }
-    if ((int64_t)t.key_of_id.size() == d->capacity) {
-      // void call: the table is insert-only, so it is rebuilt from the ids it held before
-      std::vector<int64_t> old(t.key_of_id.begin(), t.key_of_id.begin() + size0);
-      t.clear(t.T);
-      for (int64_t k0 : old) t.add(t.find(k0), k0);
+    int32_t id;
+    if (!t.free.empty()) {
+      id = *t.free.begin();
+      t.free.erase(t.free.begin());
+    } else if (t.bound() < d->capacity) {
+      id = (int32_t)t.bound();
+    } else {
+      // void call: the ids go back (holes stay holes) and the table is rebuilt from the ids it held before
+      for (int32_t f : fresh) {
+        if ((int64_t)f >= bound0) continue;
+        t.key_of_id[(size_t)f] = GK_DIR_NONE;
+        t.free.insert(f);
+      }
+      t.key_of_id.resize((size_t)bound0);
+      t.rebuild();
       return fail_dir_overflow(d->capacity, size0);
     }
-    t.add(slot, k);  // (size < capacity <= T / 2: find met an empty slot)
-    out_ids[i] = t.ids[(size_t)slot];
+    // (size < capacity <= T / 2 and at most T / 4 removed keys in place: find met the key's or an empty slot)
+    t.bind(slot, k, id);
+    fresh.push_back(id);
+    out_ids[i] = id;
   }
-  if (num_new) *num_new = (int64_t)t.key_of_id.size() - size0;
+  if (num_new) *num_new = (int64_t)fresh.size();
+  return GK_OK;
+}
+
+int gk_dir_remove(gk_dir* d, const int64_t* keys, int64_t count, int32_t* out_ids, int64_t* num_removed,
+                  void* stream) {
+  (void)stream;
+  int rc = check_dir_args(d, keys, count, out_ids, true);
+  if (rc) return rc;
+  DirTable& t = d->t;
+  int64_t removed = 0;
+  for (int64_t i = 0; i < count; ++i) {
+    const int64_t k = keys[i];
+    const int64_t slot = k == GK_DIR_NONE ? -1 : t.find(k);
+    if (!t.holds(slot, k)) {
+      out_ids[i] = -1;
+      continue;
+    }
+    const int32_t id = t.ids[(size_t)slot];
+    out_ids[i] = id;
+    t.ids[(size_t)slot] = -1;  // the key stays: its own tombstone
+    t.key_of_id[(size_t)id] = GK_DIR_NONE;
+    t.free.insert(id);
+    ++removed;
+  }
+  // as the device engine: at most T/4 removed keys keep a slot, so used slots stay <= 3T/4
+  t.dead += removed;
+  if (t.dead > (int64_t)t.T / 4) t.rebuild();
+  if (num_removed) *num_removed = removed;
   return GK_OK;
 }
 
@@ -1224,7 +1325,7 @@ int gk_dir_lookup(gk_dir* d, const int64_t* keys, int64_t count, int32_t* out_id
   for (int64_t i = 0; i < count; ++i) {
     const int64_t k = keys[i];
     const int64_t slot = k == GK_DIR_NONE ? -1 : t.find(k);
-    out_ids[i] = (slot >= 0 && t.keys[(size_t)slot] == k) ? t.ids[(size_t)slot] : -1;
+    out_ids[i] = t.holds(slot, k) ? t.ids[(size_t)slot] : -1;
   }
   return GK_OK;
 }
@@ -1243,25 +1344,14 @@ int gk_dir_import(gk_dir* d, const int64_t* keys, int64_t count, void* stream) {
   (void)stream;
   int rc = check_dir_args(d, keys, count, nullptr, false);
   if (rc) return rc;
-  if (count > d->capacity) return fail_dir_import_count(count, d->capacity);
-  for (int64_t i = 0; i < count; ++i)
-    if (keys[i] == GK_DIR_NONE) return fail_dir_import_none(i);
-  // built in a second table that replaces the first on success
-  DirTable nt;
-  nt.home = d->t.home;
-  try {
-    nt.clear(d->t.T);
-    nt.key_of_id.reserve((size_t)count);
-  } catch (...) {
-    return fail(GK_E_NOMEM, "directory: no memory for a second table");
-  }
-  for (int64_t i = 0; i < count; ++i) {
-    const int64_t slot = nt.find(keys[i]);
-    if (nt.keys[(size_t)slot] == keys[i]) return fail_dir_import_repeat(i, keys[i]);
-    nt.add(slot, keys[i]);
-  }
-  d->t = std::move(nt);
-  return GK_OK;
+  return dir_import(d, keys, count, false);
+}
+
+int gk_dir_import_sparse(gk_dir* d, const int64_t* keys, int64_t count, void* stream) {
+  (void)stream;
+  int rc = check_dir_args(d, keys, count, nullptr, false);
+  if (rc) return rc;
+  return dir_import(d, keys, count, true);
 }
 
 int gk_flush_period(const gk_set* h) { return h ? (int)std::min<int64_t>(h->P, INT32_MAX) : -1; }

@@ -2196,9 +2196,15 @@ int gk_unpack_select(gk_set* h, const int32_t* ids, int64_t count, const void* b
 
 struct gk_dir {
   int64_t capacity = 0;
-  int64_t size = 0;  // keys assigned so far
+  int64_t size = 0;   // keys held
+  int64_t bound = 0;  // one past the largest id handed out; size + nfree == bound
   int device = 0;
   GKDirTable t = {};
+  // the ids of [0, bound) that no key holds: d_free[head .. head + nfree), ascending
+  int32_t* d_free = nullptr;  // [capacity]
+  int64_t head = 0;
+  int64_t nfree = 0;
+  int64_t dead = 0;  // upper bound on slots that hold a removed key (zero after a rebuild or an import)
   // scratch of assign / import (only grows): per sample its slot and its flag,
   // scanned in place into its rank; the scan's tile sums; the control words
   uint32_t* d_slot = nullptr;
@@ -2252,11 +2258,72 @@ int dir_read_ctl(gk_dir* d, unsigned long long* ctl, hipStream_t s) {
   return GK_OK;
 }
 
-// keys[i] -> i into the cleared table t (import, and the rebuild after a void call)
+// keys[i] -> i into the cleared table t, GK_DIR_NONE entries skipped (import, and the rebuilds)
 int dir_fill(gk_dir* d, const GKDirTable& t, const int64_t* keys, int64_t count, hipStream_t s) {
   HIP_TRY(hipMemsetAsync(d->d_ctl, 0, GK_DIR_CTL_WORDS * sizeof(unsigned long long), s));
   HIP_TRY(gk_launch_dir_insert(t, keys, count, d->d_slot, d->d_ctl, s));
-  HIP_TRY(gk_launch_dir_number(t, keys, d->d_slot, nullptr, count, 0, d->d_ctl, s));
+  HIP_TRY(gk_launch_dir_number(t, keys, d->d_slot, nullptr, count, nullptr, 0, 0, d->d_ctl, s));
+  return GK_OK;
+}
+
+// The table again from the inverse array, which holds GK_DIR_NONE at free ids:
+// every slot a void call claimed or a removed key kept is empty afterwards.
+int dir_rebuild(gk_dir* d, hipStream_t s) {
+  HIP_TRY(gk_launch_dir_clear(d->t, s));
+  int rc = dir_fill(d, d->t, d->t.key_of_id, d->bound, s);  // (GK_DIR_CTL_NONE: the free ids, no error here)
+  if (rc) return rc;
+  d->dead = 0;
+  return GK_OK;
+}
+
+// d_free = the free ids of [0, bound), from the inverse array (nfree is known: bound - size)
+int dir_refresh_free(gk_dir* d, hipStream_t s) {
+  d->head = 0;
+  d->nfree = d->bound - d->size;
+  if (d->nfree > 0)
+    HIP_TRY(gk_launch_dir_free_list(d->t, d->bound, d->d_flag, d->d_sums, d->d_free, nullptr, s));
+  return GK_OK;
+}
+
+// gk_dir_import (sparse false: a GK_DIR_NONE entry is refused) and gk_dir_import_sparse
+int dir_import(gk_dir* d, const int64_t* keys, int64_t count, bool sparse, hipStream_t s) {
+  if (count > d->capacity) return fail_dir_import_count(count, d->capacity);
+  int rc = dir_ensure_scratch(d, std::max(count, d->bound));
+  if (rc) return rc;
+  GKDirTable nt;
+  rc = dir_new_table(d->t, &nt, s);
+  unsigned long long ctl[GK_DIR_CTL_WORDS] = {};
+  if (!rc) rc = dir_fill(d, nt, keys, count, s);
+  if (!rc) rc = dir_read_ctl(d, ctl, s);
+  if (!rc && !sparse && ctl[GK_DIR_CTL_NONE]) rc = fail_dir_import_none(count - (int64_t)ctl[GK_DIR_CTL_NONE]);
+  if (!rc && ctl[GK_DIR_CTL_DUP]) {
+    const int64_t idx = count - (int64_t)ctl[GK_DIR_CTL_DUP];
+    int64_t key = 0;
+    if (hipMemcpy(&key, keys + idx, sizeof(key), hipMemcpyDeviceToHost) != hipSuccess)
+      rc = fail(GK_E_HIP, "directory: device-to-host copy failed");
+    else
+      rc = fail_dir_import_repeat(idx, key);
+  }
+  if (!rc && ctl[GK_DIR_CTL_OVF]) rc = fail(GK_E_HIP, "directory: import ran out of slots");  // (count <= capacity: never)
+  if (rc) {
+    (void)hipStreamSynchronize(s);
+    dir_free_table(&nt);
+    return rc;
+  }
+  dir_free_table(&d->t);
+  d->t = nt;
+  d->bound = count;
+  d->size = count;
+  d->head = d->nfree = d->dead = 0;
+  if (sparse && ctl[GK_DIR_CTL_NONE]) {
+    // the free ids, counted by the scan
+    HIP_TRY(hipMemsetAsync(d->d_ctl, 0, GK_DIR_CTL_WORDS * sizeof(unsigned long long), s));
+    HIP_TRY(gk_launch_dir_free_list(d->t, count, d->d_flag, d->d_sums, d->d_free, d->d_ctl + GK_DIR_CTL_NEW, s));
+    rc = dir_read_ctl(d, ctl, s);
+    if (rc) return rc;
+    d->nfree = (int64_t)ctl[GK_DIR_CTL_NEW];
+    d->size = count - d->nfree;
+  }
   return GK_OK;
 }
 
@@ -2280,8 +2347,9 @@ int gk_dir_create(int64_t capacity, int device, gk_dir** out) {
   d->capacity = capacity;
   d->device = device;
   rc = dir_new_table(like, &d->t, nullptr);
-  if (!rc && !renew_dev(&d->d_ctl, GK_DIR_CTL_WORDS * sizeof(unsigned long long)))
-    rc = fail(GK_E_NOMEM, "directory: no device memory for the control words");
+  if (!rc && (!renew_dev(&d->d_ctl, GK_DIR_CTL_WORDS * sizeof(unsigned long long)) ||
+              !renew_dev(&d->d_free, (size_t)capacity * sizeof(int32_t))))
+    rc = fail(GK_E_NOMEM, "directory: no device memory for the control words and the free ids");
   if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(GK_E_HIP, "directory: clearing the table failed");
   if (rc) {
     gk_dir_destroy(d);
@@ -2295,7 +2363,7 @@ int gk_dir_destroy(gk_dir* d) {
   if (!d) return GK_OK;
   (void)hipDeviceSynchronize();
   dir_free_table(&d->t);
-  for (void* p : {(void*)d->d_slot, (void*)d->d_flag, (void*)d->d_sums, (void*)d->d_ctl})
+  for (void* p : {(void*)d->d_slot, (void*)d->d_flag, (void*)d->d_sums, (void*)d->d_ctl, (void*)d->d_free})
     if (p) (void)hipFree(p);
   delete d;
   return GK_OK;
@@ -2303,6 +2371,7 @@ int gk_dir_destroy(gk_dir* d) {
 
 int64_t gk_dir_capacity(const gk_dir* d) { return d ? d->capacity : -1; }
 int64_t gk_dir_size(const gk_dir* d) { return d ? d->size : -1; }
+int64_t gk_dir_bound(const gk_dir* d) { return d ? d->bound : -1; }
 
 int gk_dir_assign(gk_dir* d, const int64_t* keys, int64_t count, int32_t* out_ids, int64_t* num_new, void* stream) {
   int rc = check_dir_args(d, keys, count, out_ids, true);
@@ -2313,7 +2382,7 @@ int gk_dir_assign(gk_dir* d, const int64_t* keys, int64_t count, int32_t* out_id
     if (num_new) *num_new = 0;
     return GK_OK;
   }
-  rc = dir_ensure_scratch(d, std::max(count, d->size));
+  rc = dir_ensure_scratch(d, std::max(count, d->bound));
   if (rc) return rc;
   HIP_TRY(hipMemsetAsync(d->d_ctl, 0, GK_DIR_CTL_WORDS * sizeof(unsigned long long), s));
   HIP_TRY(hipMemsetAsync(d->d_ctl + GK_DIR_CTL_IDLE, 1, sizeof(unsigned long long), s));  // (any non-zero word)
@@ -2321,22 +2390,61 @@ int gk_dir_assign(gk_dir* d, const int64_t* keys, int64_t count, int32_t* out_id
   HIP_TRY(gk_launch_dir_flag(d->t, d->d_slot, count, d->d_flag, d->d_ctl, s));
   static_assert(GK_KG_BAD == 0, "the scan reads its skip word at index GK_KG_BAD");
   HIP_TRY(gk_launch_scan_u32(d->d_flag, count, d->d_sums, d->d_ctl + GK_DIR_CTL_IDLE, d->d_ctl + GK_DIR_CTL_NEW, s));
-  HIP_TRY(gk_launch_dir_number(d->t, keys, d->d_slot, d->d_flag, count, d->size, d->d_ctl, s));
+  HIP_TRY(gk_launch_dir_number(d->t, keys, d->d_slot, d->d_flag, count, d->d_free + d->head, d->nfree, d->bound,
+                               d->d_ctl, s));
   HIP_TRY(gk_launch_dir_lookup(d->t, keys, d->d_slot, count, out_ids, s));
   unsigned long long ctl[GK_DIR_CTL_WORDS];
   rc = dir_read_ctl(d, ctl, s);
   if (rc) return rc;
-  if (ctl[GK_DIR_CTL_OVF]) {
-    // void call: claimed slots cannot be released (insert-only table), so the
-    // table is rebuilt from the inverse array, which no void call has touched
-    HIP_TRY(gk_launch_dir_clear(d->t, s));
-    rc = dir_fill(d, d->t, d->t.key_of_id, d->size, s);
+  const int64_t fresh = (int64_t)ctl[GK_DIR_CTL_NEW];
+  if (ctl[GK_DIR_CTL_OVF] || fresh > d->capacity - d->size) {
+    // void call (k_dir_number wrote nothing): the slots it claimed go with a
+    // rebuild of the table from the inverse array, which no void call touches
+    rc = dir_rebuild(d, s);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return fail_dir_overflow(d->capacity, d->size);
   }
-  d->size += (int64_t)ctl[GK_DIR_CTL_NEW];
-  if (num_new) *num_new = (int64_t)ctl[GK_DIR_CTL_NEW];
+  const int64_t recycled = std::min(fresh, d->nfree);
+  d->head += recycled;
+  d->nfree -= recycled;
+  d->bound += fresh - recycled;
+  d->size += fresh;
+  if (num_new) *num_new = fresh;
+  return GK_OK;
+}
+
+// Removed keys keep their slots.  The table is rebuilt once `dead`, an upper
+// bound on such slots, passes T/4: used slots <= capacity + T/4 <= 3T/4, so a
+// batch that fits `capacity` always finds slots, and every rebuild is paid for
+// by more than T/4 removals.
+int gk_dir_remove(gk_dir* d, const int64_t* keys, int64_t count, int32_t* out_ids, int64_t* num_removed,
+                  void* stream) {
+  int rc = check_dir_args(d, keys, count, out_ids, true);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (count == 0) {
+    HIP_TRY(hipStreamSynchronize(s));
+    if (num_removed) *num_removed = 0;
+    return GK_OK;
+  }
+  rc = dir_ensure_scratch(d, std::max(count, d->bound));
+  if (rc) return rc;
+  HIP_TRY(hipMemsetAsync(d->d_ctl, 0, GK_DIR_CTL_WORDS * sizeof(unsigned long long), s));
+  HIP_TRY(gk_launch_dir_remove(d->t, keys, count, d->d_slot, out_ids, d->d_ctl, s));
+  unsigned long long ctl[GK_DIR_CTL_WORDS];
+  rc = dir_read_ctl(d, ctl, s);
+  if (rc) return rc;
+  const int64_t removed = (int64_t)ctl[GK_DIR_CTL_NEW];
+  if (removed > 0) {
+    d->size -= removed;
+    d->dead += removed;
+    rc = dir_refresh_free(d, s);
+    if (!rc && d->dead > (int64_t)d->t.T / 4) rc = dir_rebuild(d, s);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  if (num_removed) *num_removed = removed;
   return GK_OK;
 }
 
@@ -2353,9 +2461,9 @@ int gk_dir_keys(gk_dir* d, int64_t* out_keys, void* stream) {
   int rc = check_dir(d);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (d->size > 0) {
+  if (d->bound > 0) {
     if (!out_keys) return fail(GK_E_ARG, "out_keys is null");
-    HIP_TRY(hipMemcpyAsync(out_keys, d->t.key_of_id, (size_t)d->size * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(out_keys, d->t.key_of_id, (size_t)d->bound * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
   }
   HIP_TRY(hipStreamSynchronize(s));
   return GK_OK;
@@ -2364,34 +2472,13 @@ int gk_dir_keys(gk_dir* d, int64_t* out_keys, void* stream) {
 int gk_dir_import(gk_dir* d, const int64_t* keys, int64_t count, void* stream) {
   int rc = check_dir_args(d, keys, count, nullptr, false);
   if (rc) return rc;
-  if (count > d->capacity) return fail_dir_import_count(count, d->capacity);
-  hipStream_t s = (hipStream_t)stream;
-  rc = dir_ensure_scratch(d, std::max(count, d->size));
+  return dir_import(d, keys, count, false, (hipStream_t)stream);
+}
+
+int gk_dir_import_sparse(gk_dir* d, const int64_t* keys, int64_t count, void* stream) {
+  int rc = check_dir_args(d, keys, count, nullptr, false);
   if (rc) return rc;
-  GKDirTable nt;
-  rc = dir_new_table(d->t, &nt, s);
-  unsigned long long ctl[GK_DIR_CTL_WORDS] = {};
-  if (!rc) rc = dir_fill(d, nt, keys, count, s);
-  if (!rc) rc = dir_read_ctl(d, ctl, s);
-  if (!rc && ctl[GK_DIR_CTL_NONE]) rc = fail_dir_import_none(count - (int64_t)ctl[GK_DIR_CTL_NONE]);
-  if (!rc && ctl[GK_DIR_CTL_DUP]) {
-    const int64_t idx = count - (int64_t)ctl[GK_DIR_CTL_DUP];
-    int64_t key = 0;
-    if (hipMemcpy(&key, keys + idx, sizeof(key), hipMemcpyDeviceToHost) != hipSuccess)
-      rc = fail(GK_E_HIP, "directory: device-to-host copy failed");
-    else
-      rc = fail_dir_import_repeat(idx, key);
-  }
-  if (!rc && ctl[GK_DIR_CTL_OVF]) rc = fail(GK_E_HIP, "directory: import ran out of slots");  // (count <= capacity: never)
-  if (rc) {
-    (void)hipStreamSynchronize(s);
-    dir_free_table(&nt);
-    return rc;
-  }
-  dir_free_table(&d->t);
-  d->t = nt;
-  d->size = count;
-  return GK_OK;
+  return dir_import(d, keys, count, true, (hipStream_t)stream);
 }
 
 int64_t gk_num_streams(const gk_set* h) { return h ? h->S : -1; }

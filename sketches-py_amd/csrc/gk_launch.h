@@ -291,7 +291,7 @@ struct GKDirTable {
 #define GK_DIR_SLOT_FULL 0xFFFFFFFEu   // slot_of: the probe ran out of slots
 // Control words of a directory call (zeroed by the caller, but for the last):
 #define GK_DIR_CTL_OVF 0    // the table or the id space ran out
-#define GK_DIR_CTL_NEW 1    // the scan's total: keys added by this call
+#define GK_DIR_CTL_NEW 1    // the scan's total: keys added by this call (gk_dir_remove: keys removed)
 #define GK_DIR_CTL_NONE 2   // count minus the first index of a GK_DIR_NONE key (as GK_SEL_FIRST)
 #define GK_DIR_CTL_DUP 3    // import: count minus the first index of a repeated key
 #define GK_DIR_CTL_IDLE 4   // SET by the caller, cleared by k_dir_insert on meeting a slot without an id:
@@ -305,10 +305,20 @@ hipError_t gk_launch_dir_insert(const GKDirTable& t, const int64_t* keys, int64_
 // flag[i] = sample i is the first occurrence of a key without an id
 hipError_t gk_launch_dir_flag(const GKDirTable& t, const uint32_t* slot_of, int64_t count, uint32_t* flag,
                               const unsigned long long* ctl, hipStream_t stream);
-// first occurrences take id = size + rank[i] (rank NULL: id = i, and any other sample is a repeat)
+// first occurrences take id = free_ids[rank[i]] while rank[i] < nfree, then bound + rank[i] - nfree; nothing is
+// written when GK_DIR_CTL_OVF is set or GK_DIR_CTL_NEW passes nfree + capacity - bound (void call).
+// rank NULL: id = i, a GK_DIR_NONE entry leaves GK_DIR_NONE in key_of_id[i], and any other sample is a repeat
 hipError_t gk_launch_dir_number(const GKDirTable& t, const int64_t* keys, const uint32_t* slot_of,
-                                const uint32_t* rank, int64_t count, int64_t size, unsigned long long* ctl,
-                                hipStream_t stream);
+                                const uint32_t* rank, int64_t count, const int32_t* free_ids, int64_t nfree,
+                                int64_t bound, unsigned long long* ctl, hipStream_t stream);
+// gk_dir_remove: out_ids[i] = the id keys[i] held, if sample i is the first of its key in the batch, else -1;
+// the key's slot loses its id, key_of_id[id] = GK_DIR_NONE; ctl[GK_DIR_CTL_NEW] (zeroed by the caller) += keys removed
+hipError_t gk_launch_dir_remove(const GKDirTable& t, const int64_t* keys, int64_t count, uint32_t* slot_of,
+                                int32_t* out_ids, unsigned long long* ctl, hipStream_t stream);
+// free_ids[0 ..) = the ids of [0, bound) that no key holds, ascending; *total_out (device, may be NULL) = how many.
+// flag: bound words, sums: gk_scan_sums(bound) words of scratch
+hipError_t gk_launch_dir_free_list(const GKDirTable& t, int64_t bound, uint32_t* flag, unsigned long long* sums,
+                                   int32_t* free_ids, unsigned long long* total_out, hipStream_t stream);
 // out_ids[i] = id of slot_of[i], or (slot_of NULL) of keys[i] by a read-only probe; -1 if none
 hipError_t gk_launch_dir_lookup(const GKDirTable& t, const int64_t* keys, const uint32_t* slot_of, int64_t count,
                                 int32_t* out_ids, hipStream_t stream);

@@ -87,10 +87,13 @@ SYMBOLS = {
     "gk_dir_destroy": (_INT, [_P]),
     "gk_dir_capacity": (_I64, [_P]),
     "gk_dir_size": (_I64, [_P]),
+    "gk_dir_bound": (_I64, [_P]),
     "gk_dir_assign": (_INT, [_P, _P, _I64, _P, ctypes.POINTER(_I64), _P]),
+    "gk_dir_remove": (_INT, [_P, _P, _I64, _P, ctypes.POINTER(_I64), _P]),
     "gk_dir_lookup": (_INT, [_P, _P, _I64, _P, _P]),
     "gk_dir_keys": (_INT, [_P, _P, _P]),
     "gk_dir_import": (_INT, [_P, _P, _I64, _P]),
+    "gk_dir_import_sparse": (_INT, [_P, _P, _I64, _P]),
     "gk_num_streams": (_I64, [_P]),
     "gk_eps": (_D, [_P]),
     "gk_flush_period": (_INT, [_P]),

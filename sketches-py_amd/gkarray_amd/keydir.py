@@ -23,9 +23,11 @@ NO_KEY = -2 ** 63  # GK_DIR_NONE: "no key", always answers id -1
 
 
 class KeyDirectory:
-    """At most ``capacity`` int64 keys, each bound to the id ``len(dir)`` had
-    when the key was first seen.  Ids depend on the order of first occurrence
-    alone; the GPU and the host engine give the same ones."""
+    """At most ``capacity`` int64 keys, each bound to an id below ``bound``:
+    a new key takes the smallest id a removed key has left free and, when
+    there is none, ``bound`` itself, which then grows by one.  Ids depend on
+    the directory's contents and the order of first occurrence alone; the GPU
+    and the host engine give the same ones.  ``len(dir)`` counts the keys held."""
 
     def __init__(self, capacity, device=None):
         """``device`` as ``StreamSet``: a cuda (HIP) device, the default, or
@@ -46,6 +48,7 @@ class KeyDirectory:
             dev_index = device.index
         self.device = device
         self.last_new = 0
+        self.last_removed = 0
         h = ctypes.c_void_p()
         with self._ctx():
             self._check(self._lib.gk_dir_create(int(capacity), dev_index, ctypes.byref(h)))
@@ -88,6 +91,12 @@ class KeyDirectory:
     def __len__(self):
         return self._lib.gk_dir_size(self._h)
 
+    @property
+    def bound(self):
+        """One past the largest id handed out (``gk_dir_bound``):
+        ``len(self)`` plus the number of free ids."""
+        return self._lib.gk_dir_bound(self._h)
+
     def _keys(self, keys):
         """A one-dimensional int64 key tensor on the directory's device."""
         k = torch.as_tensor(keys)
@@ -104,9 +113,9 @@ class KeyDirectory:
         return k.contiguous()
 
     def assign(self, keys):
-        """``gk_dir_assign``: the ids of ``keys`` (int32 tensor), new keys
-        numbered in order of first occurrence from ``len(self)``; ``NO_KEY``
-        answers -1.  ``self.last_new`` is the number of keys added.  A batch
+        """``gk_dir_assign``: the ids of ``keys`` (int32 tensor); new keys, in
+        order of first occurrence, take the free ids in ascending order and
+        then ``bound``, ``bound + 1``, ...; ``NO_KEY`` answers -1.  ``self.last_new`` is the number of keys added.  A batch
         whose new keys do not fit raises ``GKBackendError`` (GK_E_OVERFLOW) and
         leaves the directory exactly as it was."""
         k = self._keys(keys)
@@ -117,6 +126,23 @@ class KeyDirectory:
             self._check(self._lib.gk_dir_assign(self._h, _ptr(k) if n else None, n, _ptr(out) if n else None,
                                                 ctypes.byref(new), self._sp()))
         self.last_new = new.value
+        return out[:n]
+
+    def remove(self, keys):
+        """``gk_dir_remove``: the ids the listed keys held (int32 tensor), -1
+        for a key the directory does not hold, for ``NO_KEY`` and for every
+        occurrence of a key after its first.  The ids are free for later new
+        keys; ``self.last_removed`` is the number of keys removed.  No set is
+        touched: reset the streams of the returned ids before new keys
+        inherit them (``KeyedStreamSet.remove`` does)."""
+        k = self._keys(keys)
+        n = k.numel()
+        out = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+        gone = ctypes.c_int64(0)
+        with self._ctx():
+            self._check(self._lib.gk_dir_remove(self._h, _ptr(k) if n else None, n, _ptr(out) if n else None,
+                                                ctypes.byref(gone), self._sp()))
+        self.last_removed = gone.value
         return out[:n]
 
     def lookup(self, keys):
@@ -131,29 +157,34 @@ class KeyDirectory:
         return out[:n]
 
     def keys(self):
-        """The inverse array: int64 tensor, ``keys()[id]`` holds ``id``."""
-        n = len(self)
+        """The inverse array: int64 tensor of length ``bound``, ``keys()[id]``
+        holds ``id``; ``NO_KEY`` at free ids."""
+        n = self.bound
         out = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
         with self._ctx():
             self._check(self._lib.gk_dir_keys(self._h, _ptr(out), self._sp()))
         return out[:n]
 
-    def import_keys(self, keys):
+    def import_keys(self, keys, sparse=False):
         """``gk_dir_import``: the contents become ``keys[i] -> i``.  More keys
         than ``capacity``, a ``NO_KEY`` entry or a key listed twice raise
-        ``GKBackendError`` (GK_E_ARG) and leave the old contents in place."""
+        ``GKBackendError`` (GK_E_ARG) and leave the old contents in place.
+        ``sparse=True`` (``gk_dir_import_sparse``): a ``NO_KEY`` entry is a
+        free id instead, so that ``keys()`` of a directory with free ids
+        restores it."""
         k = self._keys(keys)
         n = k.numel()
+        call = self._lib.gk_dir_import_sparse if sparse else self._lib.gk_dir_import
         with self._ctx():
-            self._check(self._lib.gk_dir_import(self._h, _ptr(k) if n else None, n, self._sp()))
+            self._check(call(self._h, _ptr(k) if n else None, n, self._sp()))
 
     def resized(self, capacity):
         """A new directory of ``capacity`` keys on this device with the same
-        bindings; this one is not changed.  A capacity below ``len(self)`` is
-        refused."""
+        bindings and free ids; this one is not changed.  A capacity below
+        ``bound`` is refused."""
         out = KeyDirectory(capacity, device=self.device)
         try:
-            out.import_keys(self.keys())
+            out.import_keys(self.keys(), sparse=True)
         except Exception:
             out.close()
             raise
@@ -164,7 +195,9 @@ class KeyedStreamSet:
     """``sketches = {}; sketches.setdefault(key, GKArray(eps)).add(value)`` for
     whole batches: a ``KeyDirectory`` in front of a ``StreamSet``.  Key ``k``
     owns stream ``directory.lookup([k])`` of ``streams``; both halves grow by
-    doubling when a batch brings more new keys than fit."""
+    doubling when a batch brings more new keys than fit.  ``remove`` is
+    ``del sketches[k]``: the stream is reset and its id goes to the next new
+    key, so keys that come and go at a steady count never grow either half."""
 
     def __init__(self, eps, capacity=1024, device=None, max_streams=None):
         capacity = int(capacity)
@@ -218,8 +251,9 @@ class KeyedStreamSet:
         """``for i: sketches[keys[i]].add(values[i])`` with new keys bound on
         the way (``gk_dir_assign`` + ``gk_ingest_keyed``); ``NO_KEY`` samples
         are skipped.  With ``quantiles=qs``: ``quantiles(qs)`` of every key
-        after the batch, float64 [len(self), len(qs)], row ``id`` for
-        ``keys()[id]``.  Raises ``GKBackendError`` (GK_E_OVERFLOW), with
+        after the batch, float64 [directory.bound, len(qs)], row ``id`` for
+        ``keys()[id]``; the row of a free id (``NO_KEY``) holds the answers of
+        an empty stream.  Raises ``GKBackendError`` (GK_E_OVERFLOW), with
         nothing changed, when the new keys would pass ``max_streams``."""
         k = self.directory._keys(keys)
         v = torch.as_tensor(values)
@@ -227,7 +261,7 @@ class KeyedStreamSet:
             raise ValueError("keys and values must be one-dimensional and of one length")
         ids = self._assign_growing(k)
         out = self.streams.ingest_keyed(ids, v, quantiles=quantiles, single=single)
-        return None if out is None else out[:len(self)]
+        return None if out is None else out[:self.directory.bound]
 
     # ----------------------------------------------------------------- query
     def _ids(self, keys):
@@ -261,7 +295,43 @@ class KeyedStreamSet:
         """``sketches[k] = GKArray(eps)`` for the listed keys; each keeps its binding."""
         self.streams.reset_select(self._ids(keys))
 
+    # --------------------------------------------------------------- removal
+    def _release(self, ids):
+        """Streams ``ids`` (no -1, no repeats) back to ``GKArray(eps)``, first:
+        a sticky error of the set surfaces before the directory changes."""
+        if ids.numel():
+            self.streams.reset_select(ids)
+
+    def remove(self, keys):
+        """``for k in keys: del sketches[k]``: the keys leave the directory,
+        their streams are reset and their ids are free for new keys.
+        ``KeyError`` names the first unknown key, with nothing changed; a key
+        listed twice is removed once."""
+        k = self.directory._keys(keys)
+        self._release(torch.unique(self._ids(k)))
+        self.directory.remove(k)
+
+    def discard(self, keys):
+        """``remove`` that ignores keys the object does not hold (and ``NO_KEY``)."""
+        k = self.directory._keys(keys)
+        ids = self.directory.lookup(k)
+        self._release(torch.unique(ids[ids >= 0]))
+        self.directory.remove(k)
+
+    def pop(self, keys, device=None):
+        """``[sketches.pop(k) for k in keys]``: a new ``StreamSet`` whose stream
+        j is the complete state of ``keys[j]`` (``streams.take``; ``device`` as
+        there: this device, another GPU or ``"cpu"``), after which the keys
+        are removed.  Eviction in one call.  ``KeyError`` as ``remove``."""
+        k = self.directory._keys(keys)
+        ids = self._ids(k)
+        out = self.streams.take(ids, device=device)
+        self._release(torch.unique(ids))
+        self.directory.remove(k)
+        return out
+
     def keys(self):
+        """``directory.keys()``: length ``directory.bound``, ``NO_KEY`` at free ids."""
         return self.directory.keys()
 
     def __len__(self):
@@ -273,13 +343,13 @@ class KeyedStreamSet:
     # ----------------------------------------------------------------- files
     def save(self, path):
         """The streams as a GKSTATE file at ``path`` and the keys beside it as
-        ``path + ".keys.npy"`` (int64, ``keys()``)."""
+        ``path + ".keys.npy"`` (int64, ``keys()``: ``NO_KEY`` at free ids)."""
         self.streams.save(path)
         np.save(os.fspath(path) + ".keys.npy", self.keys().cpu().numpy())
 
     @classmethod
     def load(cls, path, device=None, max_streams=None):
-        """The object ``save(path)`` wrote: same keys, ids and stream states."""
+        """The object ``save(path)`` wrote: same keys, ids, free ids and stream states."""
         cpu = device is not None and torch.device(device).type == "cpu"
         eps, S = peek(path, cpu=cpu)
         keys = torch.from_numpy(np.load(os.fspath(path) + ".keys.npy").astype(np.int64))
@@ -289,5 +359,5 @@ class KeyedStreamSet:
         if out.directory.capacity != S:
             raise ValueError("%d saved streams do not fit max_streams=%s" % (S, max_streams))
         out.streams.load_state(path)
-        out.directory.import_keys(keys)
+        out.directory.import_keys(keys, sparse=True)
         return out
