@@ -2,8 +2,9 @@
 //
 // Owns the per-set device state (header arrays, table arenas, pending
 // buffers), decides flush modes and table-capacity classes, and launches the
-// kernels of gk_kernels.hip on the caller's HIP stream.  Every entry point is
-// declared in include/gk_capi.h with the reference method it replaces.
+// kernels of the gk_*.hip units (gk_launch.h) on the caller's HIP stream and
+// the set's aux streams.  Every entry point is declared in include/gk_capi.h
+// with the reference method it replaces.  (Ingest / flush: ingest_call.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -87,11 +88,7 @@ struct gk_set {
   bool done_pending = false;
   // the last ingest / flush call: its inputs, kept to re-run deferred streams
   // (the caller keeps them valid until the set's next call or gk_sync)
-  struct {
-    const double* x = nullptr;
-    const int64_t* offs = nullptr;
-    int force = 0;
-    GKQuery q;
+  struct : GKBatch {
     bool may_defer = false;  // some class could run out of slots in it
   } last;
   // a gk_reset came after the call whose counters are still in flight: its
@@ -162,19 +159,25 @@ struct gk_set {
   // the flush list (k_select_check)
   int32_t* d_sel = nullptr;
   int64_t sel_words = 0;
-  bool forked = false;              // stats_fork launched on aux; stats_join / stats_abort joins it
-  bool sl_inline = false;           // no fork: stats_join launches k_stats_long on the call's stream
-  const double* sl_x = nullptr;     // (its arguments)
-  const int64_t* sl_offs = nullptr;
+  // What the call in progress still has to join on the caller's stream: set
+  // next to the launch that makes the debt (stats_fork, launch_wg), settled
+  // and cleared by join_owed alone -- on every path, errors included: the
+  // next call's begin_call zeroes counters those kernels add to.
+  struct {
+    bool wg = false;         // k_ingest_wg on aux2 (ev_wg)
+    bool aux = false;        // k_stats_long forked to aux (ev_join)
+    bool presort = false;    // the presort on aux2 / aux3 (ev_presort)
+    bool sl_inline = false;  // no fork: k_stats_long on the call's own stream, behind the ingest
+    const double* sl_x = nullptr;  // (its arguments)
+    const int64_t* sl_offs = nullptr;
+  } owed;
   // the presort of the long streams' flush batches runs here beside the short
   // streams' chains (k_stats on the caller's stream); the ingest waits for it
   hipStream_t aux2 = nullptr;
   hipStream_t aux3 = nullptr;    // the presort when k_ingest_wg runs beside it (ps.done)
-  bool presort_active = false;   // a presort of this call not yet joined on the caller's stream
   hipEvent_t ev_presort = nullptr;
   hipEvent_t ev_wg = nullptr;  // k_ingest_wg (on aux2, after the presort) done
   hipEvent_t ev_go = nullptr;  // the call's counters zeroed: k_ingest_wg may be launched (GK_WG_EARLY)
-  bool wg_early = false;       // this call's k_ingest_wg was launched by stats_fork, ahead of the chain walks
   bool wg_trace = false;       // GK_WG_TRACE=1 at creation: its stream count per completed call on stderr (tests)
   // timing: event pairs recorded around the timed launches, summed at read
   bool timing = false;        // events around the class-0 ingest launch (gk_timing_enable bit 0)
@@ -316,8 +319,7 @@ void poll(gk_set* h, bool block) {
   }
 }
 
-int promote_rounds(gk_set* h, const double* x, const int64_t* offs, int force, const GKQuery& q, hipStream_t s,
-                   bool fresh = false);
+int promote_rounds(gk_set* h, const GKBatch& a, hipStream_t s, bool fresh = false);
 int mark_done(gk_set* h, hipStream_t s, bool ingest = false);
 
 // Start of a call's device work: ONE memset zeroes every per-call counter
@@ -396,7 +398,7 @@ int replay_deferred(gk_set* h, hipStream_t s) {
     if (rb) return rb;
     h->h_ovf[0] = nd;  // pinned; the stream is synchronised below before it is reused
     HIP_TRY(hipMemcpyAsync(h->d_ovfc, h->h_ovf, sizeof(int32_t), hipMemcpyHostToDevice, s));
-    rc = promote_rounds(h, h->last.x, h->last.offs, h->last.force, h->last.q, s);
+    rc = promote_rounds(h, h->last, s);
     GK_TR("replay: enqueued rc=%d", rc);
     if (!rc) rc = mark_done(h, s);
     if (rc) return rc;
@@ -495,29 +497,36 @@ hipEvent_t timing_event(std::vector<hipEvent_t>& v, size_t& n) {
   return v[n++];
 }
 
-bool stats_fused(const gk_set* h);
-
 // One launch of class c: every stream (c == 0) or the streams of `list`
-// whose length is *count_ptr (device).  Overflowing streams go to round r's list.
-hipError_t launch_class(gk_set* h, int c, const double* x, const int64_t* offs, const int32_t* list,
-                        const int32_t* count_ptr, int r, int force, const GKQuery& q, hipStream_t stream,
-                        bool prio = false, bool wg = false, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr,
-                        int pmode = 0) {
+// whose length is *count_ptr (device).  Overflowing streams go to round r's
+// list.  L: what the caller has set already (run_ingest's class-0 launch: the
+// priority list, the presort, the stats role, the timing events; pmode of a
+// fused promotion round); the rest of the descriptor is filled here.
+hipError_t launch_class(gk_set* h, const GKBatch& a, int c, const int32_t* list, const int32_t* count_ptr, int r,
+                        hipStream_t stream, GKIngestLaunch L = GKIngestLaunch()) {
   if (c > 0 && h->st.alloc[c] == 0) return hipSuccess;  // no slot yet: no member
-  unsigned long long* work = work_counter(h, c == 0 && h->st.cap[0] == GK_SMALL_CAP && !h->big[0]);
-  if (!work) return hipErrorInvalidValue;
+  L.work = work_counter(h, c == 0 && h->st.cap[0] == GK_SMALL_CAP && !h->big[0]);
+  if (!L.work) return hipErrorInvalidValue;
   const GKPoolDev pool = pool_args(h);
-  if (h->big[c])
-    return gk_launch_ingest_big(h->st.cap[c], h->st, x, offs, list, list ? 0 : h->S, count_ptr, c, force,
-                                h->d_ws[c], h->ws_bytes[c], h->ws_blocks[c], ovf_count(h, r), ovf_list(h, r), q,
-                                work, h->d_ctr, stream);
-  return gk_launch_ingest(h->st.cap[c], h->vpl, h->st, x, offs, list, list ? 0 : h->S, count_ptr, c, force,
-                          h->d_ws[c], h->ws_bytes[c], h->ws_blocks[c], ovf_count(h, r), ovf_list(h, r), q, work,
-                          prio ? h->d_long_list : nullptr, prio ? h->d_long_count : nullptr,
-                          prio && h->ps.ws ? h->ps.ws : nullptr, prio && h->ps.ws ? h->ps.list_ws : nullptr,
-                          prio && wg ? h->ps.wg_count : nullptr,
-                          (prio && c == 0 && stats_fused(h)) ? h->fused_stats : 0, stream, ev0, ev1, &pool,
-                          pmode | overflow_direct(h, c));
+  static_cast<GKBatch&>(L) = a;
+  L.list = list;
+  L.count = list ? 0 : h->S;
+  L.count_ptr = count_ptr;
+  L.lcls = c;
+  L.cap = h->st.cap[c];
+  L.vpl = h->vpl;
+  L.ws = h->d_ws[c];
+  L.ws_bytes = h->ws_bytes[c];
+  L.ws_blocks = h->ws_blocks[c];
+  L.ovf_count = ovf_count(h, r);
+  L.ovf_list = ovf_list(h, r);
+  if (h->big[c]) {
+    L.ctr = h->d_ctr;
+    return gk_launch_ingest_big(h->st, L, stream);
+  }
+  L.pool = &pool;
+  L.pmode |= overflow_direct(h, c);
+  return gk_launch_ingest(h->st, L, stream);
 }
 
 // gk:52-59 for a batch: k_stats over every stream on `s` (it lists the
@@ -530,18 +539,49 @@ hipError_t launch_class(gk_set* h, int c, const double* x, const int64_t* offs, 
 // only lists the long streams)
 bool stats_fused(const gk_set* h) { return h->fused_stats > 0 && h->st.cap[0] == GK_SMALL_CAP; }
 
+// The one place that settles gk_set::owed: `s` waits for what the call
+// launched on the aux streams and gets the k_stats_long owed to it, each
+// entry cleared as it is settled; in this order: k_ingest_wg, k_stats_long
+// (inline or forked), the presort.  strict: stop at the first HIP failure and
+// report it; else best effort, errors ignored.  wg_only: that entry alone.
+int join_owed(gk_set* h, hipStream_t s, bool strict, bool wg_only = false) {
+#define OWED_TRY(flag, expr)   \
+  if (h->owed.flag) {          \
+    h->owed.flag = false;      \
+    if (strict) HIP_TRY(expr); \
+    else (void)(expr);         \
+  }
+  OWED_TRY(wg, hipStreamWaitEvent(s, h->ev_wg, 0));
+  if (wg_only) return GK_OK;
+  OWED_TRY(sl_inline,
+           gk_launch_stats_long(h->st, h->owed.sl_x, h->owed.sl_offs, h->d_long_list, nullptr, h->d_long_count, s));
+  OWED_TRY(aux, hipStreamWaitEvent(s, h->ev_join, 0));
+  OWED_TRY(presort, hipStreamWaitEvent(s, h->ev_presort, 0));
+#undef OWED_TRY
+  return GK_OK;
+}
+
 // A call that fails between stats_fork and stats_join: best effort, `s` still
 // waits for the aux work.
-void stats_abort(gk_set* h, hipStream_t s) {
-  if (h->wg_early) (void)hipStreamWaitEvent(s, h->ev_wg, 0);  // (launched by stats_fork: joined here too)
-  h->wg_early = false;
-  if (h->forked) (void)hipStreamWaitEvent(s, h->ev_join, 0);
-  if (h->sl_inline)
-    (void)gk_launch_stats_long(h->st, h->sl_x, h->sl_offs, h->d_long_list, nullptr, h->d_long_count, s);
-  h->sl_inline = false;
-  if (h->presort_active) (void)hipStreamWaitEvent(s, h->ev_presort, 0);
-  h->presort_active = false;
-  h->forked = false;
+void stats_abort(gk_set* h, hipStream_t s) { (void)join_owed(h, s, false); }
+
+// k_ingest_wg on aux2 behind wait_ev, over the head of the long list (the
+// longest streams: one workgroup each); go: the device word its workgroups
+// wait for (the early launch), or NULL.  The call owes its join from here on.
+int launch_wg(gk_set* h, const double* x, const int64_t* offs, int force, unsigned long long* work,
+              hipEvent_t wait_ev, const int32_t* go) {
+  GKIngestLaunch L;
+  static_cast<GKBatch&>(L) = GKBatch{x, offs, force};
+  L.list = h->d_long_list;
+  L.count_ptr = h->ps.wg_count;
+  L.ovf_count = ovf_count(h, 0);
+  L.ovf_list = ovf_list(h, 0);
+  L.work = work;
+  HIP_TRY(hipStreamWaitEvent(h->aux2, wait_ev, 0));
+  HIP_TRY(gk_launch_ingest_wg(h->st, L, h->ps, go, h->aux2));
+  HIP_TRY(hipEventRecord(h->ev_wg, h->aux2));
+  h->owed.wg = true;
+  return GK_OK;
 }
 
 int stats_fork(gk_set* h, const double* x, const int64_t* offs, hipStream_t s, int force) {
@@ -561,7 +601,6 @@ int stats_fork(gk_set* h, const double* x, const int64_t* offs, hipStream_t s, i
   // workgroups).  Read per call, like the other GK_WG switches.
   const char* early_s = getenv("GK_WG_EARLY");
   const int early_env = early_s ? atoi(early_s) : 1;
-  h->wg_early = false;
   const bool early = early_env && x && h->ps.done && h->ps.wg_count && h->aux2 && h->ps.list_ws && gk_wg_early_ok();
   if (early) HIP_TRY(hipEventRecord(h->ev_go, s));
   // the long-stream list (k_lengths) + k_long_prep, then the fork
@@ -587,11 +626,8 @@ int stats_fork(gk_set* h, const double* x, const int64_t* offs, hipStream_t s, i
   if (early && prep) {
     wwork_early = work_counter(h, false);
     if (!wwork_early) return fail(GK_E_HIP, "no hand-out counter left for k_ingest_wg");
-    HIP_TRY(hipStreamWaitEvent(h->aux2, h->ev_go, 0));
-    HIP_TRY(gk_launch_ingest_wg(h->st, x, offs, h->d_long_list, h->ps.wg_count, 0, force, ovf_count(h, 0),
-                                ovf_list(h, 0), wwork_early, h->ps, h->aux2, h->d_ctr + GK_CTR_WGGO));
-    HIP_TRY(hipEventRecord(h->ev_wg, h->aux2));
-    h->wg_early = true;
+    const int rw = launch_wg(h, x, offs, force, wwork_early, h->ev_go, h->d_ctr + GK_CTR_WGGO);
+    if (rw) return rw;
   }
   const bool presort = h->ps.list_ws && h->ps.ws && h->ps.ws_cap > 0;
   // No fork when nothing but k_stats_long would go to the aux streams and the
@@ -602,11 +638,12 @@ int stats_fork(gk_set* h, const double* x, const int64_t* offs, hipStream_t s, i
   // on the step's critical path, and a k_stats_long dispatched beside the
   // ingest grid cost the cfg3 launch 8 % (profiles/r06/r06q_*).  A wrong
   // guess costs time only: the walk is the same on either stream.
-  h->sl_inline = stats_fused(h) && !prep && !early && !presort && !h->aux2 && h->h_ctr &&
-                 h->h_ctr[GK_CTR_LONG] == 0 && !getenv("GK_SL_FORK");
-  if (h->sl_inline) {
-    h->sl_x = x;
-    h->sl_offs = offs;
+  const bool sl_inline = stats_fused(h) && !prep && !early && !presort && !h->aux2 && h->h_ctr &&
+                        h->h_ctr[GK_CTR_LONG] == 0 && !getenv("GK_SL_FORK");
+  if (sl_inline) {
+    h->owed.sl_inline = true;
+    h->owed.sl_x = x;
+    h->owed.sl_offs = offs;
   } else {
     HIP_TRY(hipEventRecord(h->ev_fork, s));
   }
@@ -615,10 +652,8 @@ int stats_fork(gk_set* h, const double* x, const int64_t* offs, hipStream_t s, i
     // early workgroup that gave up waiting for k_long_prep's word (bounded
     // spin, GK_WG_GO_TICKS); normally none are left and its workgroups leave
     // at once
-    HIP_TRY(hipStreamWaitEvent(h->aux2, h->ev_fork, 0));
-    HIP_TRY(gk_launch_ingest_wg(h->st, x, offs, h->d_long_list, h->ps.wg_count, 0, force, ovf_count(h, 0),
-                                ovf_list(h, 0), wwork_early, h->ps, h->aux2, nullptr));
-    HIP_TRY(hipEventRecord(h->ev_wg, h->aux2));
+    const int rw = launch_wg(h, x, offs, force, wwork_early, h->ev_fork, nullptr);
+    if (rw) return rw;
   }
   // Forked ahead of the small-class launch (nothing else between them on
   // `s`): `s` waits until aux has passed the fork, so that k_stats_long's
@@ -626,10 +661,10 @@ int stats_fork(gk_set* h, const double* x, const int64_t* offs, hipStream_t s, i
   // it they ran 2x longer and slowed the ingest (cfg4 x 8 shards 79 -> 84 ms
   // per step, profiles/r06/r07i_*).  Costs one cross-queue wake-up (~13 us)
   // on calls that fork (long streams: steps of tens of ms).
-  const bool sl_order = !h->sl_inline && stats_fused(h) && !presort && !h->aux2;
-  if (!h->sl_inline) {
+  const bool sl_order = !sl_inline && stats_fused(h) && !presort && !h->aux2;
+  if (!sl_inline) {
     HIP_TRY(hipStreamWaitEvent(h->aux, h->ev_fork, 0));
-    h->forked = true;
+    h->owed.aux = true;
     if (sl_order) HIP_TRY(hipEventRecord(h->ev_slgo, h->aux));
     HIP_TRY(gk_launch_stats_long(h->st, x, offs, h->d_long_list, prep ? h->d_long_n : nullptr, h->d_long_count,
                                  h->aux));
@@ -643,7 +678,7 @@ int stats_fork(gk_set* h, const double* x, const int64_t* offs, hipStream_t s, i
     HIP_TRY(hipStreamWaitEvent(ps_s, h->ev_fork, 0));
     HIP_TRY(gk_launch_presort(h->st, x, offs, h->d_long_list, h->d_long_n, h->d_long_count, h->ps, ps_s));
     HIP_TRY(hipEventRecord(h->ev_presort, ps_s));
-    h->presort_active = true;
+    h->owed.presort = true;
   }
   if (!stats_fused(h)) HIP_TRY(gk_launch_stats_short(h->st, x, offs, s));
   // (with k_ingest_wg every presorted stream is one of its streams: the
@@ -657,21 +692,9 @@ int stats_fork(gk_set* h, const double* x, const int64_t* offs, hipStream_t s, i
 }
 
 int stats_join(gk_set* h, hipStream_t s, const GKQuery& q) {
-  if (h->wg_early) {  // (run_ingest returned before joining the early k_ingest_wg)
-    h->wg_early = false;
-    HIP_TRY(hipStreamWaitEvent(s, h->ev_wg, 0));
-  }
-  if (h->sl_inline) {
-    h->sl_inline = false;
-    HIP_TRY(gk_launch_stats_long(h->st, h->sl_x, h->sl_offs, h->d_long_list, nullptr, h->d_long_count, s));
-  } else {
-    HIP_TRY(hipStreamWaitEvent(s, h->ev_join, 0));
-  }
-  h->forked = false;
-  if (h->presort_active) {
-    h->presort_active = false;
-    HIP_TRY(hipStreamWaitEvent(s, h->ev_presort, 0));
-  }
+  // (run_ingest may have returned before joining the early k_ingest_wg)
+  const int rc = join_owed(h, s, true);
+  if (rc) return rc;
   // (+ the _min/_max markers of the small-class launch's answers when it
   // carried the stats role: its chains are final here)
   HIP_TRY(gk_launch_query_list(h->st, h->d_long_list, h->d_long_count, q, stats_fused(h), s));
@@ -689,8 +712,7 @@ int stats_join(gk_set* h, hipStream_t s, const GKQuery& q) {
 // since), so after r rounds no stream is above class r: round r re-runs
 // class r only (the launches of the classes above would find their re-run
 // lists empty).
-int promote_rounds(gk_set* h, const double* x, const int64_t* offs, int force, const GKQuery& q, hipStream_t stream,
-                   bool fresh) {
+int promote_rounds(gk_set* h, const GKBatch& a, hipStream_t stream, bool fresh) {
   const int R = h->st.nclass;
   GKPoolDev pool = pool_args(h);
   bool ran = true;  // a launch ran in the previous round (round 0: class 0)
@@ -717,10 +739,11 @@ int promote_rounds(gk_set* h, const double* x, const int64_t* offs, int force, c
     for (int c = r; c < c_end; ++c) fuse = fuse && h->st.alloc[c] > 0 && !h->big[c];
     if (fuse) {
       ran = false;
+      GKIngestLaunch promote;
+      promote.pmode = 1;
       for (int c = r; c < c_end; ++c) {
         ran = true;
-        HIP_TRY(launch_class(h, c, x, offs, ovf_list(h, r - 1), ovf_count(h, r - 1), r, force, q, stream, false, false,
-                             nullptr, nullptr, 1));
+        HIP_TRY(launch_class(h, a, c, ovf_list(h, r - 1), ovf_count(h, r - 1), r, stream, promote));
         if (g_trace) {
           HIP_TRY(hipStreamSynchronize(stream));
           GK_TR("round %d: class %d promoted + re-run (fused)", r, c);
@@ -737,7 +760,7 @@ int promote_rounds(gk_set* h, const double* x, const int64_t* offs, int force, c
     ran = false;
     for (int c = r; c < (fresh ? r + 1 : R); ++c) {
       ran |= h->st.alloc[c] > 0;  // (launch_class launches nothing without slots)
-      HIP_TRY(launch_class(h, c, x, offs, h->d_rerun[c], rcnt + c, r, force, q, stream));
+      HIP_TRY(launch_class(h, a, c, h->d_rerun[c], rcnt + c, r, stream));
       if (g_trace) {
         HIP_TRY(hipStreamSynchronize(stream));
         GK_TR("round %d: class %d re-run done", r, c);
@@ -747,25 +770,22 @@ int promote_rounds(gk_set* h, const double* x, const int64_t* offs, int force, c
   return GK_OK;
 }
 
-int run_ingest(gk_set* h, const double* x, const int64_t* offs, int force, hipStream_t stream,
-               const GKQuery& q = GKQuery(), bool prio = false) {
-  if (!offs) offs = h->d_zero_offs;
+int run_ingest(gk_set* h, const GKBatch& call, hipStream_t stream, bool prio) {
   const int R = h->st.nclass;
   const bool fresh = h->no_members;  // (promote_rounds clears it)
-  h->last.x = x;
-  h->last.offs = offs;
-  h->last.force = force;
-  h->last.q = q;
+  GKBatch& a = h->last;
+  a = call;
+  if (!a.offs) a.offs = h->d_zero_offs;
   h->last.may_defer = false;
   for (int c = 1; c < R; ++c) h->last.may_defer |= h->st.alloc[c] < h->S;
   // (the call's counters were zeroed by begin_call)
   // timing covers the class-0 batch launch of gk_ingest (x given) only
-  const bool timed = h->timing && x != nullptr;
+  const bool timed = h->timing && a.x != nullptr;
   // the longest presorted streams of an ingest: one workgroup each, on aux2
   // right behind their presort, beside the class-0 launch (which skips them)
   // (a stream whose batches are not presorted -- no workspace yet, or it did
   // not fit -- is ranked unsorted there)
-  const bool wg = prio && x != nullptr && h->ps.wg_count && h->aux2 && h->ps.list_ws;
+  const bool wg = prio && a.x != nullptr && h->ps.wg_count && h->aux2 && h->ps.list_ws;
   // The small-class launch alone records the pair as part of its dispatch
   // (the kernel's own start and end; two marker packets around it cost the
   // step ~12 us of dispatch gaps); with k_ingest_wg beside it the markers
@@ -779,32 +799,45 @@ int run_ingest(gk_set* h, const double* x, const int64_t* offs, int force, hipSt
     t0 = timed ? timing_event(h->tev_flush, h->n_flush) : nullptr;
   }
   if (t0 && !ext) HIP_TRY(hipEventRecord(t0, stream));
-  if (wg && !h->wg_early) {
+  if (wg && !h->owed.wg) {  // (not launched early by stats_fork)
     unsigned long long* wwork = work_counter(h, false);
     if (!wwork) return fail(GK_E_HIP, "no hand-out counter left for k_ingest_wg");
     // (behind k_long_prep, which counts its streams, and the call's counter
     // reset: the fork point; the presort, when there is one, is already
     // ordered after it on aux2)
-    HIP_TRY(hipStreamWaitEvent(h->aux2, h->ev_fork, 0));
-    HIP_TRY(gk_launch_ingest_wg(h->st, x, offs, h->d_long_list, h->ps.wg_count, 0, force, ovf_count(h, 0),
-                                ovf_list(h, 0), wwork, h->ps, h->aux2));
-    HIP_TRY(hipEventRecord(h->ev_wg, h->aux2));
+    const int rl = launch_wg(h, a.x, a.offs, a.force, wwork, h->ev_fork, nullptr);
+    if (rl) return rl;
   }
-  const hipError_t lc = launch_class(h, 0, x, offs, nullptr, nullptr, 0, force, q, stream, prio && x != nullptr, wg,
-                                     ext ? t0 : nullptr, ext ? t1x : nullptr);
+  // class 0; an ingest's batch: the long streams first (presorted batches;
+  // not k_ingest_wg's streams), the stats role in the small class
+  GKIngestLaunch L0;
+  if (prio && a.x != nullptr) {
+    L0.prio = h->d_long_list;
+    L0.prio_count = h->d_long_count;
+    if (h->ps.ws) {
+      L0.psort = h->ps.ws;
+      L0.prio_ws = h->ps.list_ws;
+    }
+    if (wg) L0.prio_skip = h->ps.wg_count;
+    if (stats_fused(h)) L0.fused_stats = h->fused_stats;
+  }
+  if (ext) {
+    L0.ev_start = t0;
+    L0.ev_stop = t1x;
+  }
+  const hipError_t lc = launch_class(h, a, 0, nullptr, nullptr, 0, stream, L0);
   // (its overflow entries feed the promotion rounds below).  k_ingest_wg is
   // joined on every path once launched: the next call's begin_call zeroes the
   // counter block it adds to
-  if (wg) HIP_TRY(hipStreamWaitEvent(stream, h->ev_wg, 0));
-  h->wg_early = false;
+  const int rw = join_owed(h, stream, true, true);
+  if (rw) return rw;
   HIP_TRY(lc);
   // (with k_ingest_wg beside it, the timed span is both: the call's batch ingest)
   hipEvent_t t1 = (timed && !ext) ? timing_event(h->tev_flush, h->n_flush) : nullptr;
   if (t1) HIP_TRY(hipEventRecord(t1, stream));
   if (!h->no_members)
-    for (int c = 1; c < R; ++c)
-      HIP_TRY(launch_class(h, c, x, offs, h->d_list[c], h->d_ctr + GK_CTR_LCNT + c, 0, force, q, stream));
-  return promote_rounds(h, x, offs, force, q, stream, fresh);
+    for (int c = 1; c < R; ++c) HIP_TRY(launch_class(h, a, c, h->d_list[c], h->d_ctr + GK_CTR_LCNT + c, 0, stream));
+  return promote_rounds(h, a, stream, fresh);
 }
 
 // The capacity-level ladder of the synchronous folds (merge, merge_compress,
@@ -893,12 +926,35 @@ int flush_listed(gk_set* h, const int32_t* list, int64_t n, hipStream_t s) {
   return run_fold(h, a, kMergeOverflow, s);
 }
 
+// The device work of one ingest / flush call on `s`: the one body of gk_ingest,
+// gk_ingest_quantiles, gk_flush, gk_quantiles and flush_source, which keep
+// their checks, early returns, grow_pools and query staging (their order is
+// the error precedence).  with_stats: the call adds values -- the gk:52-59
+// chains run beside the ingest, the long streams go first, the long-stream
+// count comes back with the counters.  The join and the readback are enqueued
+// whatever the ingest returned; the first failure of the three is returned.
+int ingest_call(gk_set* h, const double* x, const int64_t* offs, int force, const GKQuery& q, bool with_stats,
+                hipStream_t s, bool sticky = true) {
+  int rc = sticky ? take_sticky(h) : GK_OK;
+  if (!rc) rc = begin_call(h, s);
+  if (rc) return rc;
+  if (with_stats) {
+    rc = stats_fork(h, x, offs, s, force);
+    if (rc) {
+      stats_abort(h, s);
+      return rc;
+    }
+  }
+  rc = run_ingest(h, GKBatch{x, offs, force, q}, s, with_stats);
+  const int rj = with_stats ? stats_join(h, s, q) : GK_OK;  // joined on every path
+  const int rd = mark_done(h, s, with_stats);
+  return rc ? rc : (rj ? rj : rd);
+}
+
 // other.merge_compress() of every stream of a fold's source -- unconditional
 // in the reference (gk:126, 137) -- as one batch flush, settled on return.
 int flush_source(gk_set* src, hipStream_t s, void* stream) {
-  int rc = begin_call(src, s);
-  if (!rc) rc = run_ingest(src, nullptr, nullptr, 2, s);
-  if (!rc) rc = mark_done(src, s);
+  int rc = ingest_call(src, nullptr, nullptr, 2, GKQuery(), false, s, false);
   if (!rc) rc = gk_sync(src, stream);
   return rc;
 }
@@ -1173,18 +1229,7 @@ int gk_ingest(gk_set* h, const double* values, const int64_t* offsets, void* str
   if (h->S == 0) return GK_OK;
   hipStream_t s = (hipStream_t)stream;
   rc = grow_pools(h, s);
-  if (!rc) rc = take_sticky(h);
-  if (!rc) rc = begin_call(h, s);
-  if (rc) return rc;
-  rc = stats_fork(h, values, offsets, s, 0);
-  if (rc) {
-    stats_abort(h, s);
-    return rc;
-  }
-  rc = run_ingest(h, values, offsets, 0, s, GKQuery(), true);
-  const int rj = stats_join(h, s, GKQuery());  // joined on every path
-  const int rd = mark_done(h, s, true);
-  return rc ? rc : (rj ? rj : rd);
+  return rc ? rc : ingest_call(h, values, offsets, 0, GKQuery(), true, s);
 }
 
 // The grouping scratch for `count` samples (and, grouped: the set-owned
@@ -1300,12 +1345,7 @@ int gk_flush(gk_set* h, void* stream) {
   if (h->S == 0) return GK_OK;
   hipStream_t s = (hipStream_t)stream;
   rc = grow_pools(h, s);
-  if (!rc) rc = take_sticky(h);
-  if (!rc) rc = begin_call(h, s);
-  if (rc) return rc;
-  rc = run_ingest(h, nullptr, nullptr, 1, s);
-  const int rd = mark_done(h, s);
-  return rc ? rc : rd;
+  return rc ? rc : ingest_call(h, nullptr, nullptr, 1, GKQuery(), false, s);
 }
 
 int gk_sync(gk_set* h, void* stream) {
@@ -1379,14 +1419,9 @@ int gk_quantiles(gk_set* h, const double* qs, int nq, double* out, int mode, voi
   rc = prepare_query(h, qs, nq, out, mode, s, &q);
   if (rc) return rc;
   if (nq == 0 || h->S == 0) return GK_OK;
-  rc = take_sticky(h);
-  if (!rc) rc = begin_call(h, s);
-  if (rc) return rc;
   // gk:197-198: pending values are flushed first (state mutation); the
   // quantiles are answered in the same launch from the flushed table
-  rc = run_ingest(h, nullptr, nullptr, 1, s, q);
-  const int rd = mark_done(h, s);
-  return rc ? rc : rd;
+  return ingest_call(h, nullptr, nullptr, 1, q, false, s);
 }
 
 int gk_ingest_quantiles(gk_set* h, const double* values, const int64_t* offsets, const double* qs, int nq,
@@ -1403,20 +1438,9 @@ int gk_ingest_quantiles(gk_set* h, const double* values, const int64_t* offsets,
   if (rc) return rc;
   if (h->S == 0) return GK_OK;
   if (nq == 0) return gk_ingest(h, values, offsets, stream);
-  rc = take_sticky(h);
-  if (!rc) rc = begin_call(h, s);
-  if (rc) return rc;
-  rc = stats_fork(h, values, offsets, s, 1);
-  if (rc) {
-    stats_abort(h, s);
-    return rc;
-  }
   // add every value (gk:49-61), then quantiles() (gk:187-232): flush the
   // leftover pending values and answer from the LDS-resident table
-  rc = run_ingest(h, values, offsets, 1, s, q, true);
-  const int rj = stats_join(h, s, q);  // joined on every path
-  const int rd = mark_done(h, s, true);
-  return rc ? rc : (rj ? rj : rd);
+  return ingest_call(h, values, offsets, 1, q, true, s);
 }
 
 int gk_stats(gk_set* h, int64_t* n, double* mn, double* mx, double* sum, double* avg, int32_t* table_size,

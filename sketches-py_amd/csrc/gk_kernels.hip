@@ -4274,16 +4274,9 @@ int gk_num_cu() { return num_cu(); }
 int gk_wg_early_ok() { return num_cu() >= 2 * GK_WG_MAX; }
 
 template <int CAP, int VPL>
-static hipError_t launch_ingest_t(const GKState& st, const double* x, const int64_t* offs,
-                                  const int32_t* list, int64_t count, const int32_t* count_ptr, int lcls,
-                                  int force, int cap,
-                                  unsigned char* ws, size_t ws_bytes, int64_t ws_blocks,
-                                  int32_t* ovf_count, int32_t* ovf_list, const GKQuery& q,
-                                  unsigned long long* work, const int32_t* prio, const int32_t* prio_count,
-                                  const double* psort, const int64_t* prio_ws, const int32_t* prio_skip, hipStream_t stream,
-                                  const GKPoolDev& pool, int pmode) {
-  if (count <= 0 && !count_ptr) return hipSuccess;
-  if (!work) return hipErrorInvalidValue;
+static hipError_t launch_ingest_t(const GKState& st, const GKIngestLaunch& a, hipStream_t stream) {
+  if (a.count <= 0 && !a.count_ptr) return hipSuccess;
+  if (!a.work) return hipErrorInvalidValue;
   int64_t grid;
   if (CAP > 0) {
     // one resident wave per slot; streams are handed out through `work`
@@ -4296,60 +4289,47 @@ static hipError_t launch_ingest_t(const GKState& st, const double* x, const int6
     });
     grid = (int64_t)num_cu() * occ;
   } else {
-    grid = ws_blocks;
+    grid = a.ws_blocks;
   }
-  if (!prio && !count_ptr && grid > count) grid = count;
+  if (!a.prio && !a.count_ptr && grid > a.count) grid = a.count;
   if (grid < 1) grid = 1;
-  hipLaunchKernelGGL((k_ingest<CAP, VPL>), dim3((unsigned)grid), dim3(64), 0, stream, st, x, offs, list,
-                     count, count_ptr, lcls, force, cap, ws, ws_bytes, ovf_count, ovf_list, q.qs, q.nq, q.out,
-                     q.mode, work, prio, prio_count, psort, prio_ws, prio_skip, pool, pmode);
+  const bool lds = CAP > 0;  // (an LDS class takes no workspace)
+  hipLaunchKernelGGL((k_ingest<CAP, VPL>), dim3((unsigned)grid), dim3(64), 0, stream, st, a.x, a.offs, a.list,
+                     a.count, a.count_ptr, a.lcls, a.force, a.cap, lds ? nullptr : a.ws, lds ? 0 : a.ws_bytes,
+                     a.ovf_count, a.ovf_list, a.q.qs, a.q.nq, a.q.out, a.q.mode, a.work, a.prio, a.prio_count,
+                     a.psort, a.prio_ws, a.prio_skip, a.pool ? *a.pool : GKPoolDev{}, a.pmode);
   return hipGetLastError();
 }
 
 template <int CAP>
-static hipError_t launch_ingest_vpl(int vpl, const GKState& st, const double* x, const int64_t* offs,
-                                    const int32_t* list, int64_t count, const int32_t* count_ptr, int lcls,
-                                    int force, int cap, unsigned char* ws,
-                                    size_t ws_bytes, int64_t ws_blocks, int32_t* ovf_count, int32_t* ovf_list,
-                                    const GKQuery& q, unsigned long long* work, const int32_t* prio,
-                                    const int32_t* prio_count, const double* psort, const int64_t* prio_ws, const int32_t* prio_skip,
-                                    hipStream_t stream, const GKPoolDev& pool, int pmode) {
-#define GK_L(V) launch_ingest_t<CAP, V>(st, x, offs, list, count, count_ptr, lcls, force, cap, ws, ws_bytes, ws_blocks, \
-                                        ovf_count, ovf_list, q, work, prio, prio_count, psort, prio_ws, prio_skip, stream, \
-                                        pool, pmode)
-  switch (vpl) {
-    case 1: return GK_L(1);
-    case 2: return GK_L(2);
-    case 4: return GK_L(4);
-    case 8: return GK_L(8);
-    case 16: return GK_L(16);
+static hipError_t launch_ingest_vpl(const GKState& st, const GKIngestLaunch& a, hipStream_t stream) {
+  switch (a.vpl) {
+    case 1: return launch_ingest_t<CAP, 1>(st, a, stream);
+    case 2: return launch_ingest_t<CAP, 2>(st, a, stream);
+    case 4: return launch_ingest_t<CAP, 4>(st, a, stream);
+    case 8: return launch_ingest_t<CAP, 8>(st, a, stream);
+    case 16: return launch_ingest_t<CAP, 16>(st, a, stream);
     default: return hipErrorInvalidValue;
   }
-#undef GK_L
 }
 
 template <int VPL>
-static hipError_t launch_ingest_small(const GKState& st, const double* x, const int64_t* offs, const int32_t* list,
-                                      int64_t count, int force, int32_t* ovf_count, int32_t* ovf_list,
-                                      const GKQuery& q, unsigned long long* work, int fused_stats,
-                                      hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+static hipError_t launch_ingest_small(const GKState& st, const GKIngestLaunch& a, hipStream_t stream) {
+  const int64_t count = a.count;
   if (count <= 0) return hipSuccess;
-  if (!work) return hipErrorInvalidValue;
-  const bool fs_launch = fused_stats > 0 && x && !list;
+  if (!a.work) return hipErrorInvalidValue;
+  const bool fs_launch = a.fused_stats > 0 && a.x && !a.list;
   // Two builds of each kernel: GK_SMALL_WAVES (7) waves per SIMD, and 6 for
   // launches of few streams per wave (occupancy queried once per device and
-  // kernel: the register counts may differ).
+  // kernel: the register counts may differ).  [stats role][6 waves]
+  static const decltype(&k_ingest_small<VPL, false>) kern[2][2] = {
+      {k_ingest_small<VPL, false>, k_ingest_small<VPL, false, 6>},
+      {k_ingest_small<VPL, true>, k_ingest_small<VPL, true, 6>}};
   static std::atomic<int> occ_cache[2][2][GK_MAX_DEV];
   auto occ_of = [&](bool fs, bool w6) -> int {
     return per_device(occ_cache[fs][w6], [fs, w6](int) {
       int o = 0;
-      if (fs) {
-        if (w6) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, k_ingest_small<VPL, true, 6>, 64, 0);
-        else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, k_ingest_small<VPL, true>, 64, 0);
-      } else {
-        if (w6) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, k_ingest_small<VPL, false, 6>, 64, 0);
-        else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, k_ingest_small<VPL, false>, 64, 0);
-      }
+      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kern[fs][w6], 64, 0);
       return o;
     });
   };
@@ -4373,94 +4353,64 @@ static hipError_t launch_ingest_small(const GKState& st, const double* x, const 
   // (only for the batch launch over every stream: x given, no list)
   int nstat = 0;
   if (fs_launch) {
-    const int64_t want = std::max<int64_t>(1, (int64_t)num_cu() * fused_stats / 8);  // eighths of a wave per CU
+    const int64_t want = std::max<int64_t>(1, (int64_t)num_cu() * a.fused_stats / 8);  // eighths of a wave per CU
     nstat = (int)(grid < want ? grid : want);
   }
   // pacing needs ingest-only waves in every part (stats waves wait for them)
   const int pace = nstat > 0 && grid >= 4 * (int64_t)nstat && grid >= 8 * GK_WORK_PARTS ? 1 : 0;
   static const int lag = getenv("GK_FS_LAG") ? atoi(getenv("GK_FS_LAG")) : GK_FS_LAG_DEFAULT;
-  if (list) return hipErrorInvalidValue;  // class 0 over every stream only
-  // (ev0 / ev1: recorded by the dispatch itself -- the kernel's own start and
-  // end -- when given)
-#define GK_SMALL_LAUNCH(FS_, W_)                                                                              \
-  hipExtLaunchKernelGGL((k_ingest_small<VPL, FS_, W_>), dim3((unsigned)grid), dim3(64), 0, stream, ev0, ev1, 0, st, x, \
-                        offs, count, force, ovf_count, ovf_list, q.qs, q.nq, q.out, q.mode, work, nstat, pace, lag)
-  if (nstat > 0) {
-    if (w6) GK_SMALL_LAUNCH(true, 6);
-    else GK_SMALL_LAUNCH(true, GK_SMALL_WAVES);
-  } else {
-    if (w6) GK_SMALL_LAUNCH(false, 6);
-    else GK_SMALL_LAUNCH(false, GK_SMALL_WAVES);
-  }
-#undef GK_SMALL_LAUNCH
+  if (a.list) return hipErrorInvalidValue;  // class 0 over every stream only
+  hipExtLaunchKernelGGL(kern[nstat > 0][w6], dim3((unsigned)grid), dim3(64), 0, stream, a.ev_start, a.ev_stop, 0, st,
+                        a.x, a.offs, count, a.force, a.ovf_count, a.ovf_list, a.q.qs, a.q.nq, a.q.out, a.q.mode,
+                        a.work, nstat, pace, lag);
   return hipGetLastError();
 }
 
 size_t gk_ingest_ws_bytes(int cap, int vpl) { return gk_flush_ws_bytes(cap, vpl); }
 size_t gk_big_ws_bytes(int cap, int P) { return gk_big_ws_bytes_dev(cap, P); }
 
-hipError_t gk_launch_ingest_big(int cap, const GKState& st, const double* x, const int64_t* offs,
-                                const int32_t* list, int64_t count, const int32_t* count_ptr, int lcls, int force,
-                                unsigned char* ws, size_t ws_bytes, int64_t ws_blocks, int32_t* ovf_count,
-                                int32_t* ovf_list, const GKQuery& q, unsigned long long* work, int32_t* ctr,
-                                hipStream_t stream) {
-  if (count <= 0 && !count_ptr) return hipSuccess;
-  if (!ws || ws_blocks <= 0 || !work || !ctr || ws_bytes < gk_big_ws_bytes_dev(cap, st.P)) return hipErrorInvalidValue;
-  int64_t grid = ws_blocks;
-  if (!count_ptr && grid > count) grid = count;
+hipError_t gk_launch_ingest_big(const GKState& st, const GKIngestLaunch& a, hipStream_t stream) {
+  if (a.count <= 0 && !a.count_ptr) return hipSuccess;
+  if (!a.ws || a.ws_blocks <= 0 || !a.work || !a.ctr || a.ws_bytes < gk_big_ws_bytes_dev(a.cap, st.P))
+    return hipErrorInvalidValue;
+  int64_t grid = a.ws_blocks;
+  if (!a.count_ptr && grid > a.count) grid = a.count;
   if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(k_ingest_big, dim3((unsigned)grid), dim3(64), 0, stream, st, x, offs, list, count, count_ptr,
-                     lcls, force, cap, ws, ws_bytes, ovf_count, ovf_list, q.qs, q.nq, q.out, q.mode, work, ctr);
+  hipLaunchKernelGGL(k_ingest_big, dim3((unsigned)grid), dim3(64), 0, stream, st, a.x, a.offs, a.list, a.count,
+                     a.count_ptr, a.lcls, a.force, a.cap, a.ws, a.ws_bytes, a.ovf_count, a.ovf_list, a.q.qs, a.q.nq,
+                     a.q.out, a.q.mode, a.work, a.ctr);
   return hipGetLastError();
 }
 
-hipError_t gk_launch_ingest(int cap, int vpl, const GKState& st, const double* x, const int64_t* offs,
-                            const int32_t* list, int64_t count, const int32_t* count_ptr, int lcls, int force,
-                            unsigned char* ws, size_t ws_bytes,
-                            int64_t ws_blocks, int32_t* ovf_count, int32_t* ovf_list, const GKQuery& q,
-                            unsigned long long* work, const int32_t* prio, const int32_t* prio_count,
-                            const double* psort, const int64_t* prio_ws, const int32_t* prio_skip, int fused_stats,
-                            hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, const GKPoolDev* pool,
-                            int pmode) {
-  const GKPoolDev nopool{};
-  const GKPoolDev& pl = pool ? *pool : nopool;
-  if (pmode && !pool) return hipErrorInvalidValue;
-  switch (cap) {
+hipError_t gk_launch_ingest(const GKState& st, const GKIngestLaunch& a, hipStream_t stream) {
+  if (a.pmode && !a.pool) return hipErrorInvalidValue;
+  switch (a.cap) {
     case SMALL_CAP:
-      if (list || count_ptr || lcls != 0 || pmode) return hipErrorInvalidValue;  // class 0 over every stream only
-      if (vpl == 1)
-        return launch_ingest_small<1>(st, x, offs, list, count, force, ovf_count, ovf_list, q, work, fused_stats, stream,
-                                      ev_start, ev_stop);
-      if (vpl == 2)
-        return launch_ingest_small<2>(st, x, offs, list, count, force, ovf_count, ovf_list, q, work, fused_stats, stream,
-                                      ev_start, ev_stop);
+      if (a.list || a.count_ptr || a.lcls != 0 || a.pmode) return hipErrorInvalidValue;  // class 0 over every stream only
+      if (a.vpl == 1) return launch_ingest_small<1>(st, a, stream);
+      if (a.vpl == 2) return launch_ingest_small<2>(st, a, stream);
       return hipErrorInvalidValue;
     case 2048:
-      return launch_ingest_vpl<2048>(vpl, st, x, offs, list, count, count_ptr, lcls, force, cap, nullptr, 0, 0,
-                                     ovf_count, ovf_list, q, work, prio, prio_count, psort, prio_ws, prio_skip, stream,
-                                     pl, pmode);
+      return launch_ingest_vpl<2048>(st, a, stream);
     default:
-      if (!ws || ws_blocks <= 0) return hipErrorInvalidValue;
-      return launch_ingest_vpl<0>(vpl, st, x, offs, list, count, count_ptr, lcls, force, cap, ws, ws_bytes,
-                                  ws_blocks, ovf_count, ovf_list, q, work, prio, prio_count, psort, prio_ws, prio_skip, stream,
-                                  pl, pmode);
+      if (!a.ws || a.ws_blocks <= 0) return hipErrorInvalidValue;
+      return launch_ingest_vpl<0>(st, a, stream);
   }
 }
 
-hipError_t gk_launch_ingest_wg(const GKState& st, const double* x, const int64_t* offs, const int32_t* long_list,
-                               const int32_t* wg_count, int lcls, int force, int32_t* ovf_count, int32_t* ovf_list,
-                               unsigned long long* work, const GKPresort& ps, hipStream_t stream,
-                               const int32_t* go) {
-  if (st.S <= 0 || !ps.wg_count || !work) return hipSuccess;
+hipError_t gk_launch_ingest_wg(const GKState& st, const GKIngestLaunch& a, const GKPresort& ps, const int32_t* go,
+                               hipStream_t stream) {
+  if (st.S <= 0 || !ps.wg_count || !a.work) return hipSuccess;
   // (at most GK_WG_MAX streams: the count is only known on the device; the
   // spare workgroups find the hand-out exhausted and leave)
   // raised wave priority (GK_WG_PRIO=0: off): the workgroups' flush chains
   // are the cfg5 critical path; co-resident waves of the one-wave launch and
   // the chain walks wait (cfg5 39.4 -> 39.15 ms, profiles/r05/r05x_*)
   static const int wg_prio = getenv("GK_WG_PRIO") ? atoi(getenv("GK_WG_PRIO")) : 1;
-  hipLaunchKernelGGL(k_ingest_wg, dim3(GK_WG_MAX), dim3(GK_WG_T), 0, stream, st, x, offs, long_list, wg_count, lcls,
-                     force, ovf_count, ovf_list, work, (const double*)ps.ws, (const int64_t*)ps.list_ws,
-                     (const int32_t*)ps.done, ps.done ? gk_presort_reg_grid(st) : 0, wg_prio, go);
+  hipLaunchKernelGGL(k_ingest_wg, dim3(GK_WG_MAX), dim3(GK_WG_T), 0, stream, st, a.x, a.offs, a.list, a.count_ptr,
+                     a.lcls, a.force, a.ovf_count, a.ovf_list, a.work, (const double*)ps.ws,
+                     (const int64_t*)ps.list_ws, (const int32_t*)ps.done, ps.done ? gk_presort_reg_grid(st) : 0, wg_prio,
+                     go);
   return hipGetLastError();
 }
 

@@ -28,39 +28,71 @@ size_t gk_ingest_ws_bytes(int cap, int vpl);
 // k_ingest_big (any capacity, any flush period): bytes of one block's workspace
 size_t gk_big_ws_bytes(int cap, int P);
 #define GK_WORK_BYTES 2048  // 8 hand-out counters + 8 stats-role batch counters, one 128-byte line each
-// `work`: device counters of the launch's dynamic stream hand-out, ZEROED BY THE CALLER
-// (GK_WORK_BYTES for the small-class launch, 8 bytes for the others; gk_capi.cpp
-// zeroes every counter of a call with one memset, GK_CALL_* below).
-// cap GK_SMALL_CAP / 2048: LDS kernels; any other cap: global workspace ws (ws_bytes per block, ws_blocks blocks)
-// list/count (host count) or list/count_ptr (device count): the streams of a class-lcls launch
-// (list NULL: every stream, class 0); listed streams no longer in class lcls are skipped.
-hipError_t gk_launch_ingest(int cap, int vpl, const GKState& st, const double* x, const int64_t* offs,
-                            const int32_t* list, int64_t count, const int32_t* count_ptr, int lcls, int force,
-                            unsigned char* ws, size_t ws_bytes,
-                            int64_t ws_blocks, int32_t* ovf_count, int32_t* ovf_list, const GKQuery& q,
-                            unsigned long long* work, const int32_t* prio, const int32_t* prio_count,
-                            const double* psort, const int64_t* prio_ws, const int32_t* prio_skip, int fused_stats,
-                            hipStream_t stream, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
-                            const struct GKPoolDev* pool = nullptr, int pmode = 0);
-// (ev_start / ev_stop: the small-class launch records them as part of its
-// dispatch -- hipExtLaunchKernel, the kernel's own start and end -- instead of
-// two marker packets around it; other classes ignore them.  pool / pmode:
-// the promotion rounds' fused steps, k_ingest's pmode)
-// The unbounded class (tables beyond 32768 entries; every class when P > 1024):
-// one wave per stream over ws (ws_bytes >= gk_big_ws_bytes(cap, P) per block,
-// ws_blocks blocks); list / count / count_ptr / lcls / force / q as above;
-// ctr: the set's GK_CTR_* counters (GK_CTR_FATAL: per-stream count limit).
-hipError_t gk_launch_ingest_big(int cap, const GKState& st, const double* x, const int64_t* offs,
-                                const int32_t* list, int64_t count, const int32_t* count_ptr, int lcls, int force,
-                                unsigned char* ws, size_t ws_bytes, int64_t ws_blocks, int32_t* ovf_count,
-                                int32_t* ovf_list, const GKQuery& q, unsigned long long* work, int32_t* ctr,
-                                hipStream_t stream);
-// `fused_stats` > 0: the small-class batch launch (x given, no list) also
-// walks the gk:52-59 stats of every stream of at most GK_STATS_LONG values,
-// in that many waves per CU (then requires the lengths-only k_lengths before).
-// `prio` / `prio_count` (device, may be NULL): streams handed out first by the
-// capacity-class kernels (the long streams of the batch, longest first);
-// `psort` / `prio_ws`: their presorted flush batches (GKPresort), or NULL.
+// the set's counter block and the classes' lists (GK_CTR_* below)
+struct GKPoolDev {
+  int32_t* ctr;
+  int32_t* rcnt;  // this round's re-run list lengths (one per class)
+  int32_t* list[GK_MAX_CLASSES];
+  int32_t* rerun[GK_MAX_CLASSES];
+  int32_t* defer;  // S entries
+};
+// What every launch of one ingest / flush call shares
+struct GKBatch {
+  const double* x = nullptr;      // the batch: offs = S + 1 offsets into x (x NULL: flush only, zero offsets)
+  const int64_t* offs = nullptr;
+  int force = 0;  // flush mode: 0 automatic flushes only, 1 also the pending rest, 2 merge_compress() of every stream
+  GKQuery q;
+};
+// One ingest / flush launch of one capacity class: the host fills this struct
+// (gk_capi.cpp launch_class) and the launchers unpack it at the kernel launch.
+struct GKIngestLaunch : GKBatch {
+  // list/count (host count) or list/count_ptr (device count): the streams of a class-lcls launch
+  // (list NULL: every stream, class 0); listed streams no longer in class lcls are skipped.
+  const int32_t* list = nullptr;
+  int64_t count = 0;
+  const int32_t* count_ptr = nullptr;
+  int lcls = 0;
+  // cap GK_SMALL_CAP / 2048: LDS kernels; any other cap: global workspace ws (ws_bytes per block, ws_blocks
+  // blocks).  The unbounded class (k_ingest_big: tables beyond 32768 entries; every class when P > 1024):
+  // one wave per stream over ws, ws_bytes >= gk_big_ws_bytes(cap, P).
+  int cap = 0;
+  int vpl = 0;  // (k_ingest_big ignores it)
+  unsigned char* ws = nullptr;
+  size_t ws_bytes = 0;
+  int64_t ws_blocks = 0;
+  // the streams that outgrew the class
+  int32_t* ovf_count = nullptr;
+  int32_t* ovf_list = nullptr;
+  // device counters of the launch's dynamic stream hand-out, ZEROED BY THE
+  // CALLER (GK_WORK_BYTES for the small-class launch, 8 bytes for the others;
+  // gk_capi.cpp zeroes every counter of a call with one memset, GK_CALL_* below)
+  unsigned long long* work = nullptr;
+  // prio / prio_count (device, may be NULL): streams handed out first by the
+  // capacity-class kernels (the long streams of the batch, longest first);
+  // psort / prio_ws: their presorted flush batches (GKPresort), or NULL;
+  // prio_skip: the head of that list k_ingest_wg takes (the launch skips it).
+  // For gk_launch_ingest_wg: list = the long list, count_ptr = its stream count.
+  const int32_t* prio = nullptr;
+  const int32_t* prio_count = nullptr;
+  const double* psort = nullptr;
+  const int64_t* prio_ws = nullptr;
+  const int32_t* prio_skip = nullptr;
+  // > 0: the small-class batch launch (x given, no list) also walks the
+  // gk:52-59 stats of every stream of at most GK_STATS_LONG values, in that
+  // many eighths of a wave per CU (then requires the lengths-only k_lengths before)
+  int fused_stats = 0;
+  // the small-class launch records them as part of its dispatch (hipExtLaunchKernel, the kernel's own
+  // start and end) instead of two marker packets around it; other classes ignore them
+  hipEvent_t ev_start = nullptr;
+  hipEvent_t ev_stop = nullptr;
+  // the promotion rounds' fused steps (k_ingest's pmode); pmode != 0 needs pool
+  const GKPoolDev* pool = nullptr;
+  int pmode = 0;
+  // k_ingest_big only: the set's GK_CTR_* counters (GK_CTR_FATAL: per-stream count limit)
+  int32_t* ctr = nullptr;
+};
+hipError_t gk_launch_ingest(const GKState& st, const GKIngestLaunch& a, hipStream_t stream);
+hipError_t gk_launch_ingest_big(const GKState& st, const GKIngestLaunch& a, hipStream_t stream);
 // k_stats over every stream; streams longer than GK_STATS_LONG values are put
 // on long_list (S entries), sorted longest first, with their pre-call n in
 // long_n, for gk_launch_stats_long, which may run on another HIP stream beside
@@ -80,12 +112,12 @@ struct GKPresort {
   int32_t* done = nullptr;     // device, 1 value: k_presort_reg's finished waves (k_ingest_wg runs beside
                                // the presort and takes presorted batches once all are done); NULL: after it
 };
-// one workgroup per stream for the first *wg_count streams of the long list
-// (class lcls = 0 of the 2048 class only); the prio k_ingest launch skips them
-hipError_t gk_launch_ingest_wg(const GKState& st, const double* x, const int64_t* offs, const int32_t* long_list,
-                               const int32_t* wg_count, int lcls, int force, int32_t* ovf_count, int32_t* ovf_list,
-                               unsigned long long* work, const GKPresort& ps, hipStream_t stream,
-                               const int32_t* go = nullptr);
+// one workgroup per stream for the first *a.count_ptr streams of the long list
+// a.list (class lcls = 0 of the 2048 class only); the prio k_ingest launch
+// skips them.  go (device, may be NULL): the word the workgroups wait for
+// before they start their streams (k_long_prep sets it)
+hipError_t gk_launch_ingest_wg(const GKState& st, const GKIngestLaunch& a, const GKPresort& ps, const int32_t* go,
+                               hipStream_t stream);
 // the long-stream list + every stream's pre-call n (k_lengths)
 hipError_t gk_launch_stats(const GKState& st, const int64_t* offs, int32_t* long_list, int32_t* long_count,
                            hipStream_t stream);
@@ -371,13 +403,6 @@ hipError_t gk_launch_promote(const GKState& st, const int32_t* list, int64_t cou
 static_assert(GK_CTR_RCNT + 4 * (GK_MAX_CLASSES + 1) <= GK_CTR_OVFC, "re-run counts fit below the overflow counts");
 static_assert(GK_CTR_PSDONE < GK_CALL_WORK / 4, "counters fit below the hand-out block");
 static_assert((GK_CTR_CALL * 4) % 64 == 0 && (GK_CALL_BYTES - GK_CTR_CALL * 4) % 16 == 0, "aligned per-call memset");
-struct GKPoolDev {
-  int32_t* ctr;
-  int32_t* rcnt;  // this round's re-run list lengths (one per class)
-  int32_t* list[GK_MAX_CLASSES];
-  int32_t* rerun[GK_MAX_CLASSES];
-  int32_t* defer;  // S entries
-};
 // k_promote_dev over list[0 .. *count): level -1 -> class cls+1 (ingest
 // overflow: joins the re-run list, or the defer list when that class has no
 // free slot), -2 -> class cls+1 (import), level >= 0 -> class `level` if below it
