@@ -27,7 +27,7 @@
  *    and re-run from them by the host runtime before the next call proceeds.
  *    gk_merge, gk_rollup, gk_quantiles_select, gk_flush_select,
  *    gk_reset_select, gk_stats_select, gk_ranks, gk_ranks_select,
- *    gk_merge_compress, gk_import, gk_save / gk_load, gk_pack_select_bytes,
+ *    gk_ranks_keyed, gk_merge_compress, gk_import, gk_save / gk_load, gk_pack_select_bytes,
  *    gk_pack_select, gk_unpack_select and gk_num_promoted synchronise before
  *    returning; so do the key directory's calls (gk_dir_*, an object of its
  *    own).
@@ -280,6 +280,58 @@ int gk_stats_select(gk_set* set, const int32_t* ids, int64_t count,
 int gk_ranks(gk_set* set, const double* xs, int nx, int64_t* lo, int64_t* hi, void* stream);
 int gk_ranks_select(gk_set* set, const int32_t* ids, int64_t count,
                     const double* xs, int nx, int64_t* lo, int64_t* hi, void* stream);
+
+/* Keyed rank queries: rank bounds per (stream id, value) sample -- "where does
+ * this value sit in the distribution of the series it belongs to?", for every
+ * sample of a batch in one call (the query-side counterpart of
+ * gk_ingest_keyed; ids as the key directory hands them out).
+ *  - Rows.  Row i belongs to the sample (ids[i], xs[i]), i in [0, count).  `lo`,
+ *    `hi` and `n` are int64[count].
+ *  - Memory.  `ids` (int32), `xs` (float64), `lo`, `hi` and `n` are device
+ *    memory for the GPU engine, host memory for the CPU engine.  Any of the
+ *    three outputs may be NULL, but not all three.
+ *  - Answer.  For ids[i] in [0, S), (lo[i], hi[i]) is exactly what
+ *    gk_ranks_select(set, &ids[i], 1, &xs[i], 1, ...) answers on the state after
+ *    the flush below: the four rules of the rank contract above,
+ *    integer-exact.  n[i] is that stream's _n.  Ids may repeat any number of
+ *    times and come in any order.
+ *  - Negative ids.  A negative id is "no stream", as in gk_ingest_keyed and as
+ *    gk_dir_lookup answers for an unknown key: the row gets lo = hi = n = 0,
+ *    the answer of an empty sketch.  xs[i] of such a row is not examined and
+ *    may be NaN.
+ *  - GK_E_ARG, from the call itself, before anything is mutated or written:
+ *    count outside [0, 2^31-1]; a NULL `ids` or `xs` with count > 0; all three
+ *    outputs NULL; an id >= S; a NaN xs[i] on a row whose id is >= 0.  The
+ *    message names the smallest offending sample index and its id or the word
+ *    NaN; a sample with both faults is reported by its id.
+ *  - count == 0 returns GK_OK after the argument checks and touches nothing.
+ *  - Flush rule: gk_ranks_select's rule, applied to the streams that occur in
+ *    ids.  Such a stream with n > 0 and pending values runs merge_compress()
+ *    first, once; one with nothing pending is NOT compressed again.  Streams
+ *    that do not occur stay bit-identical (GPU engine: class and slot too).
+ *  - GK_E_OVERFLOW as for gk_ranks_select: the stream that outgrew the last
+ *    capacity class keeps its pre-call state, the other occurring streams have
+ *    been flushed, no output is written.
+ *  - Synchronisation.  gk_sync first (deferred streams of the previous call are
+ *    re-run, a sticky error of it is returned instead of doing the work); the
+ *    call synchronises before returning.
+ *  - Scratch (GPU engine; owned by the set, only grows, freed by gk_destroy):
+ *    the grouping scratch of gk_ingest_keyed, its grouped-batch buffers
+ *    included (free once the leading gk_sync has settled an in-flight keyed
+ *    ingest) -- the samples are grouped by id with their sample index as the
+ *    payload -- plus the index payload itself and the selection scratch.  Per
+ *    sample: 8 bytes of index payload + 8 bytes grouped + the pair buffers of
+ *    gk_group_by_key (24 bytes for S > 65536, 16 for 256 < S <= 65536, 4 for
+ *    S <= 256) + 0.25 byte of digit counts, 40.25 bytes at most; per set:
+ *    8 (S+1) bytes of offsets, S/8 bytes of bitmap and 4 bytes per distinct
+ *    occurring stream (at most 4 min(count, S)).  GK_E_NOMEM is returned
+ *    before anything is mutated.
+ *  - GK_RANKK_CHUNK=c (environment, read per call; tests) sets the number of
+ *    grouped samples one wave of the GPU engine's kernel takes (default 1024):
+ *    a multiple of 64, >= 64, anything else is GK_E_ARG.  The answers do not
+ *    depend on it. */
+int gk_ranks_keyed(gk_set* set, const int32_t* ids, const double* xs, int64_t count,
+                   int64_t* lo, int64_t* hi, int64_t* n, void* stream);
 
 /* GKArray.merge(other) (gk:111-154), stream by stream, as the left fold
  * dst.merge(srcs[0]); dst.merge(srcs[1]); ...  Like the reference it mutates

@@ -742,6 +742,46 @@ int gk_ranks_select(gk_set* h, const int32_t* ids, int64_t count, const double* 
   return GK_OK;
 }
 
+// rank bounds per (stream id, value) sample: the checks in sample order, the
+// flush over the distinct occurring streams, then every row read-only
+int gk_ranks_keyed(gk_set* h, const int32_t* ids, const double* xs, int64_t count, int64_t* lo, int64_t* hi, int64_t* n,
+                   void* stream) {
+  (void)stream;
+  int rc = check_set(h);
+  if (!rc) rc = check_rank_keyed_args(ids, xs, count, lo, hi, n);
+  if (rc || count == 0) return rc;
+  for (int64_t k = 0; k < count; ++k)
+    if (ids[k] >= h->S || (ids[k] >= 0 && std::isnan(xs[k]))) return fail_rank_keyed_sample(k, ids[k], h->S);
+  std::vector<int32_t> uniq;
+  try {
+    std::vector<bool> seen((size_t)h->S, false);
+    for (int64_t k = 0; k < count; ++k) {
+      if (ids[k] < 0 || seen[(size_t)ids[k]]) continue;  // (negative: "no stream")
+      seen[(size_t)ids[k]] = true;
+      uniq.push_back(ids[k]);
+    }
+  } catch (...) {
+    return fail(GK_E_NOMEM, "selection scratch for %lld streams failed", (long long)h->S);
+  }
+  parallel_for((int64_t)uniq.size(), h->threads, [&](int64_t k) {
+    Stream& st = h->st[uniq[k]];
+    if (st.n > 0) flush_if_pending(h, st);  // gk:166-167
+  });
+  // (read-only from here: rows of a repeated stream may be answered in parallel)
+  parallel_for(count, h->threads, [&](int64_t k) {
+    int64_t l = 0, u = 0, cnt = 0;
+    if (ids[k] >= 0) {
+      const Stream& st = h->st[ids[k]];
+      rank_row(st, xs + k, 1, &l, &u);
+      cnt = st.n;
+    }
+    if (lo) lo[k] = l;
+    if (hi) hi[k] = u;
+    if (n) n[k] = cnt;
+  });
+  return GK_OK;
+}
+
 int gk_merge(gk_set* dst, gk_set* const* srcs, int nsrcs, void* stream) {
   (void)stream;
   int rc = check_merge_args(dst, srcs, nsrcs);

@@ -159,6 +159,10 @@ struct gk_set {
   // the flush list (k_select_check)
   int32_t* d_sel = nullptr;
   int64_t sel_words = 0;
+  // gk_ranks_keyed: the sample indices the group-by carries as its payload
+  // (rk_idx_cap doubles, bit-cast int64; made on first use, only grown)
+  double* rk_idx = nullptr;
+  int64_t rk_idx_cap = 0;
   // What the call in progress still has to join on the caller's stream: set
   // next to the launch that makes the debt (stats_fork, launch_wg), settled
   // and cleared by join_owed alone -- on every path, errors included: the
@@ -1163,7 +1167,7 @@ int gk_destroy(gk_set* h) {
                   h->ps.list_ws, h->ps.list_b0, h->ps.ws,    h->ps.ws_need,  st.rtab,        st.n0,
                   h->d_defer, h->d_roll_prog,
                   h->kg.ids[0], h->kg.ids[1], h->kg.vals[0], h->kg.vals[1],  h->kg.hist,     h->kg.sums,
-                  h->kg.call, h->kg_vals,    h->kg_offs,     h->d_sel};
+                  h->kg.call, h->kg_vals,    h->kg_offs,     h->d_sel,       h->rk_idx};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (int c = 0; c < GK_MAX_CLASSES; ++c)
@@ -1622,6 +1626,72 @@ int gk_ranks_select(gk_set* h, const int32_t* ids, int64_t count, const double* 
   rc = flush_listed(h, sel.list, sel.nflush, s);
   if (rc) return rc;  // (GK_E_OVERFLOW: lo and hi are not written)
   HIP_TRY(gk_launch_rank(h->st, ids, count, h->d_qs, nx, lo, hi, s));
+  return select_end(h, s);
+}
+
+// ---- keyed rank queries: bounds per (stream id, value) sample (k_rank_keyed)
+
+// GK_RANKK_CHUNK (tests): the grouped samples one wave takes
+static int rank_keyed_chunk(int* chunk) {
+  *chunk = GK_RANKK_CHUNK_DEFAULT;
+  const char* e = getenv("GK_RANKK_CHUNK");
+  if (!e) return GK_OK;
+  char* end = nullptr;
+  const long c = strtol(e, &end, 10);
+  if (end == e || *end || c < 64 || c % 64 || c > INT32_MAX - 63)
+    return fail(GK_E_ARG, "GK_RANKK_CHUNK=%s is not a multiple of 64 >= 64 (below 2^31)", e);
+  *chunk = (int)c;
+  return GK_OK;
+}
+
+int gk_ranks_keyed(gk_set* h, const int32_t* ids, const double* xs, int64_t count, int64_t* lo, int64_t* hi, int64_t* n,
+                   void* stream) {
+  int chunk = 0;
+  int rc = check_set(h);
+  if (!rc) rc = check_rank_keyed_args(ids, xs, count, lo, hi, n);
+  if (!rc) rc = rank_keyed_chunk(&chunk);
+  if (!rc) rc = gk_sync(h, stream);
+  if (rc || count == 0) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  // every scratch before the first launch: GK_E_NOMEM mutates nothing.  (The
+  // stream is idle after gk_sync and an in-flight keyed ingest is settled:
+  // its grouped batch in kg_vals / kg_offs is free.)
+  rc = ensure_group_scratch(h, count, true, s);
+  if (!rc && count > h->rk_idx_cap) {
+    h->rk_idx_cap = 0;
+    if (!renew_dev(&h->rk_idx, (size_t)count * sizeof(double)))
+      return fail(GK_E_NOMEM, "index payload for %lld samples failed", (long long)count);
+    h->rk_idx_cap = count;
+  }
+  if (!rc) rc = ensure_select_scratch(h, count, true, 0);
+  if (rc) return rc;
+  // ONE kernel over the samples: id range (negative ids pass), NaN on live
+  // rows, the flush list -- nothing is mutated before its verdict is read back
+  const int64_t bm = select_bitmap_words(h, true);
+  int32_t* const ctl = h->d_sel;
+  int32_t* const list = ctl + GK_SEL_WORDS + bm;
+  HIP_TRY(hipMemsetAsync(ctl, 0, (size_t)(GK_SEL_WORDS + bm) * sizeof(int32_t), s));
+  HIP_TRY(gk_launch_rank_keyed_check(h->st, ids, xs, count, ctl, reinterpret_cast<uint32_t*>(ctl + GK_SEL_WORDS), list,
+                                     h->rk_idx, s));
+  HIP_TRY(hipMemcpyAsync(h->h_ovf, ctl, GK_SEL_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (h->h_ovf[GK_SEL_BAD]) {
+    const int64_t first = count - (int64_t)(uint32_t)h->h_ovf[GK_SEL_FIRST];
+    int32_t id = 0;
+    HIP_TRY(hipMemcpy(&id, ids + first, sizeof(int32_t), hipMemcpyDeviceToHost));
+    return fail_rank_keyed_sample(first, id, h->S);
+  }
+  if (h->S == 0) {  // (every id is negative)
+    for (int64_t* o : {lo, hi, n})
+      if (o) HIP_TRY(hipMemsetAsync(o, 0, (size_t)count * sizeof(int64_t), s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return GK_OK;
+  }
+  rc = flush_listed(h, list, h->h_ovf[GK_SEL_COUNT], s);
+  if (rc) return rc;  // (GK_E_OVERFLOW: no output is written)
+  // the stable group-by of the samples by id, payload = sample index
+  HIP_TRY(gk_launch_group_by_key(h->kg, ids, h->rk_idx, count, h->S, h->kg_vals, h->kg_offs, s));
+  HIP_TRY(gk_launch_rank_keyed(h->st, ids, xs, count, h->kg_vals, h->kg_offs, chunk, lo, hi, n, s));
   return select_end(h, s);
 }
 

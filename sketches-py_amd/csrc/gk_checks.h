@@ -64,6 +64,24 @@ int check_select_args(const int32_t* ids, int64_t count) {
   return GK_OK;
 }
 
+// keyed rank arguments (gk_ranks_keyed), ahead of the per-sample checks
+int check_rank_keyed_args(const int32_t* ids, const double* xs, int64_t count, const int64_t* lo, const int64_t* hi,
+                          const int64_t* n) {
+  int rc = check_count(count);
+  if (rc) return rc;
+  if (count > 0 && (!ids || !xs)) return fail(GK_E_ARG, "ids or xs is null");
+  if (!lo && !hi && !n) return fail(GK_E_ARG, "lo, hi and n are all null");
+  return GK_OK;
+}
+
+// the first offending sample of gk_ranks_keyed: its id if that is >= S, else its NaN
+int fail_rank_keyed_sample(int64_t index, int32_t id, int64_t S) {
+  if (id >= S)
+    return fail(GK_E_ARG, "ids[%lld] = %d lies outside [0, %lld) (negative ids are skipped)", (long long)index, id,
+                (long long)S);
+  return fail(GK_E_ARG, "xs[%lld] is NaN (ids[%lld] = %d)", (long long)index, (long long)index, id);
+}
+
 // gk_merge: the source list, and every source's eps and stream count against dst's
 template <typename Set>
 int check_merge_args(const Set* dst, Set* const* srcs, int nsrcs) {

@@ -81,6 +81,13 @@ __device__ __forceinline__ int64_t wave_incl_max_i64(int64_t v, int /*lane*/) {
   return v;
 }
 
+// lane l's int64 in every lane (two v_readlane; l wave-uniform)
+__device__ __forceinline__ int64_t gk_readlane_i64(int64_t v, int l) {
+  const int lo = __builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)v, l);
+  const int hi = __builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), l);
+  return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
+}
+
 __device__ __forceinline__ int wave_sum_i32(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

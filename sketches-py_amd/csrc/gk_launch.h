@@ -304,6 +304,24 @@ inline int64_t gk_group_sums(int64_t count) {
 // id >= S leaves its outputs alone, except that out_offsets becomes all zero.
 hipError_t gk_launch_group_by_key(const GKGroupScratch& sc, const int32_t* ids, const double* values, int64_t count,
                                   int64_t S, double* out_values, int64_t* out_offsets, hipStream_t stream);
+// ---- keyed rank queries (gk_rankkeyed.hip): bounds per (stream id, value) sample ----
+// k_rank_keyed_check over the samples, mutating no stream state: ctl as
+// k_select_check's (GK_SEL_*; zeroed by the caller with the bitmap) -- GK_SEL_BAD
+// for an id >= S or a NaN xs[i] on a row with id >= 0, GK_SEL_FIRST count minus
+// the first such index; negative ids pass; the occurring streams with n > 0 and
+// pending values into list, each once.  payload[i] = the int64 i, bit-cast:
+// what the group-by carries beside ids[i].
+hipError_t gk_launch_rank_keyed_check(const GKState& st, const int32_t* ids, const double* xs, int64_t count,
+                                      int32_t* ctl, uint32_t* bitmap, int32_t* list, double* payload,
+                                      hipStream_t stream);
+// k_rank_keyed: gidx / goffs = gk_launch_group_by_key's outputs for (ids,
+// payload); row i of lo / hi / n (any may be NULL) = the rank bounds of xs[i]
+// in stream ids[i] and its n, zeros for a negative id.  One wave per `chunk`
+// grouped samples (a multiple of 64).
+#define GK_RANKK_CHUNK_DEFAULT 1024
+hipError_t gk_launch_rank_keyed(const GKState& st, const int32_t* ids, const double* xs, int64_t count,
+                                const double* gidx, const int64_t* goffs, int chunk, int64_t* lo, int64_t* hi,
+                                int64_t* n, hipStream_t stream);
 // ---- key directory (gk_dir.hip): int64 keys -> int32 ids, a device hash table ----
 // Exclusive scan in place of n uint32 values whose sum stays below 2^32 (the
 // same k_scan_* kernels); *total_out (device, may be NULL) = the sum.  skip

@@ -53,13 +53,6 @@ __global__ __launch_bounds__(256) void k_lengths(GKState st, const int64_t* __re
   if (offs[s + 1] - offs[s] > GK_STATS_LONG) long_list[atomicAdd(long_count, 1)] = (int32_t)s;
 }
 
-// lane l's int64 in every lane (two v_readlane; l wave-uniform)
-__device__ __forceinline__ int64_t gk_readlane_i64(int64_t v, int l) {
-  const int lo = __builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)v, l);
-  const int hi = __builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), l);
-  return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-}
-
 // ===========================================================================
 // Rank bounds of one stream from its flushed table (DESIGN.md section 5,
 // "k_rank"; the reference has no rank()): for every threshold x the pair

@@ -285,6 +285,34 @@ class KeyedStreamSet:
     def cdf(self, keys, xs):
         return self.streams.cdf_select(self._ids(keys), xs)
 
+    def _sample_args(self, keys, values):
+        """(ids, values) of per-sample queries: ``directory.lookup``, never an
+        assignment -- an unknown key and ``NO_KEY`` are id -1, "no stream"."""
+        k = self.directory._keys(keys)
+        v = values if isinstance(values, torch.Tensor) else torch.as_tensor(values, dtype=torch.float64)
+        if v.dim() != 1 or v.numel() != k.numel():
+            raise ValueError("keys and values must be one-dimensional and of one length")
+        return self.directory.lookup(k), v
+
+    def ranks_keyed(self, keys, values):
+        """``(lo, hi)`` of ``StreamSet.ranks_keyed``: row i bounds the count of
+        values <= ``values[i]`` in the sketch of ``keys[i]``.  No key is bound:
+        an unknown key or ``NO_KEY`` gives (0, 0), the answer of an empty
+        sketch, never a ``KeyError``."""
+        ids, v = self._sample_args(keys, values)
+        lo, hi, _ = self.streams.ranks_keyed(ids, v)
+        return lo, hi
+
+    def score(self, keys, values):
+        """Where each sample sits in the distribution of its own key: float64
+        [len(keys)], ``StreamSet.cdf_keyed`` -- ``(lo + hi) / (2 n)``, NaN for
+        an unknown key, ``NO_KEY`` or an empty sketch.  Scoring a batch against
+        the history BEFORE it joins it is ``s = k.score(keys, v); k.add(keys,
+        v)``.  Like ``quantiles``, ``score`` flushes the pending values of the
+        streams it touches."""
+        ids, v = self._sample_args(keys, values)
+        return self.streams.cdf_keyed(ids, v)
+
     def stats(self, keys):
         return self.streams.stats_select(self._ids(keys))
 

@@ -464,6 +464,62 @@ class StreamSet:
         lo, hi = self.ranks_select(i, xs)
         return self._cdf(lo, hi, self.stats_select(i)["n"])
 
+    def _keyed_out(self, want, count, name):
+        """An output of ``ranks_keyed``, as ``_rank_out`` for one dimension."""
+        if want is None or want is False:
+            return None, None
+        if want is True:
+            t = torch.empty(max(count, 1), dtype=torch.int64, device=self.device)
+            return t[:count], t
+        if not isinstance(want, torch.Tensor) or want.dtype != torch.int64 or want.device != self.device \
+                or not want.is_contiguous() or tuple(want.shape) != (count,):
+            raise ValueError("%s must be True, False or a contiguous int64 tensor of shape (%d,) on %s"
+                             % (name, count, self.device))
+        return want, (want if want.numel() else torch.empty(1, dtype=torch.int64, device=self.device))
+
+    def ranks_keyed(self, ids, xs, lo=True, hi=True, n=False):
+        """Rank bounds per sample (``gk_ranks_keyed``): row i is
+        ``ranks_select([ids[i]], [xs[i]])`` -- where ``xs[i]`` sits in the
+        distribution of stream ``ids[i]`` -- and, with ``n``, that stream's
+        count.  Returns ``(lo, hi, n)``, int64 device tensors [len(ids)]; None
+        for an output not asked for; an int64 tensor [len(ids)] on the set's
+        device is written in place.  Ids may repeat and come in any order; a
+        negative id is "no stream" (``KeyDirectory.lookup`` of an unknown key):
+        its row is (0, 0, 0) and its x may be NaN.  An id >= num_streams or a
+        NaN x on a live row raises ``GKBackendError`` (GK_E_ARG) with nothing
+        changed.  The occurring streams with pending values are flushed first,
+        as ``ranks_select`` does.  ``ids`` is int32, or int64 at the cost of a
+        range check and a conversion pass; ``xs`` becomes float64 on the set's
+        device."""
+        i = torch.as_tensor(ids)
+        # (a Python list goes straight to float64, not through torch's float32 default)
+        x = xs if isinstance(xs, torch.Tensor) else torch.as_tensor(xs, dtype=torch.float64)
+        if i.dim() != 1 or x.dim() != 1:
+            raise ValueError("ids and xs must be one-dimensional")
+        if i.numel() != x.numel():
+            raise ValueError("ids and xs must have the same length (%d vs %d)" % (i.numel(), x.numel()))
+        if i.numel() > 2 ** 31 - 1:
+            raise ValueError("at most 2^31-1 samples per call")
+        i, x = self._ids_i32(i), self._dev(x, torch.float64)
+        K = i.numel()
+        lo_t, lo_p = self._keyed_out(lo, K, "lo")
+        hi_t, hi_p = self._keyed_out(hi, K, "hi")
+        n_t, n_p = self._keyed_out(n, K, "n")
+        with self._ctx():
+            try:
+                self._check(self._lib.gk_ranks_keyed(self._h, _ptr(i) if K else None, _ptr(x) if K else None, K,
+                                                     _ptr(lo_p), _ptr(hi_p), _ptr(n_p), self._sp()))
+            finally:
+                self._inflight = None  # (the call synchronised)
+        return lo_t, hi_t, n_t
+
+    def cdf_keyed(self, ids, xs):
+        """Point estimate per sample of stream ``ids[i]``'s share of values <=
+        ``xs[i]``: float64 [len(ids)], ``(lo + hi) / (2 n)`` of ``ranks_keyed``;
+        NaN where n == 0, so also for a negative id."""
+        lo, hi, n = self.ranks_keyed(ids, xs, n=True)
+        return (lo + hi).to(torch.float64) / (2.0 * n.to(torch.float64))
+
     # ------------------------------------------------------------------ export
     def tables(self):
         """All tables in CSR form: (offs int64[S+1], v f64, g i32, d i32)."""
