@@ -30,7 +30,8 @@
  *    gk_ranks_keyed, gk_merge_compress, gk_import, gk_save / gk_load, gk_pack_select_bytes,
  *    gk_pack_select, gk_unpack_select and gk_num_promoted synchronise before
  *    returning; so do the key directory's calls (gk_dir_*, an object of its
- *    own).
+ *    own).  gk_rank_ingest_keyed synchronises for its rank half's checks and
+ *    flush and then only enqueues (see there).
  *  - Limits.  Any finite eps > 0 with int(1/eps)+1 < 2^24 is accepted (the
  *    reference: any eps; eps > 1 gives a flush period of 1, gk:60); tables grow through capacity classes up to 2^27 entries per
  *    stream (the last classes are allocated on first use).  One stream may
@@ -332,6 +333,59 @@ int gk_ranks_select(gk_set* set, const int32_t* ids, int64_t count,
  *    depend on it. */
 int gk_ranks_keyed(gk_set* set, const int32_t* ids, const double* xs, int64_t count,
                    int64_t* lo, int64_t* hi, int64_t* n, void* stream);
+
+/* Keyed score-and-ingest: rank each sample against the history of its stream,
+ * then add it -- the scoring loop "s = score(batch); add(batch)" in one call.
+ *  - Definition.  Exactly gk_ranks_keyed(set, ids, xs, count, lo, hi, n, stream)
+ *    followed by gk_ingest_keyed(set, ids, xs, count, qs, nq, out, mode, stream):
+ *    every sample is ranked against its stream's state BEFORE any value of this
+ *    batch is added (the state after gk_ranks_keyed's flush of the occurring
+ *    streams); then the batch is added, in arrival order per stream; then,
+ *    nq > 0, quantiles(qs) of every stream as gk_ingest_quantiles answers them.
+ *    lo / hi / n, out and the complete state of every stream -- table, pending
+ *    values, n/_min/_max/_sum/_avg (GPU engine: capacity class and slot too) --
+ *    are bit-identical to what the two calls give.  The samples are grouped by
+ *    id ONCE, not once per half.
+ *  - Memory and rows as gk_ranks_keyed (ids, xs, lo, hi, n) and gk_ingest_keyed
+ *    (qs host, out float64[S*nq]).  Unlike gk_ranks_keyed, lo, hi and n may ALL
+ *    be NULL: the call is then gk_ingest_keyed with the refusals below -- no
+ *    rank is taken, so no stream is flushed ahead of the ingest.
+ *  - Negative ids get the rows lo = hi = n = 0, are not ingested, and their
+ *    xs[i] is not examined.
+ *  - GK_E_ARG, from the call itself, before anything is mutated or written:
+ *    count outside [0, 2^31-1]; a NULL `ids` or `xs` with count > 0; an id >= S;
+ *    a NaN xs[i] on a row whose id is >= 0 (message and smallest offending
+ *    index as gk_ranks_keyed; a sample with both faults is reported by its id);
+ *    qs, nq, out and mode as gk_ingest_quantiles checks them; a bad
+ *    GK_RANKK_CHUNK.  A NaN value therefore CANNOT be added through this call
+ *    (gk_ingest_keyed adds it as the reference does): a rank of NaN has no
+ *    meaning.  An id >= S is never the asynchronous error it is for
+ *    gk_ingest_keyed.
+ *  - count == 0 runs the argument checks and gk_sync and then is
+ *    gk_ingest_keyed with count == 0 (nq > 0: exactly gk_quantiles).  S == 0:
+ *    the rows are zero, nothing else happens.
+ *  - GK_E_OVERFLOW of the rank half's flush: gk_ranks_keyed's rule -- no output
+ *    is written and NOTHING is ingested; the stream that outgrew the last
+ *    capacity class keeps its pre-call state, the other occurring streams have
+ *    been flushed.  Errors of the ingest half are asynchronous, exactly as for
+ *    gk_ingest_keyed (GK_E_OVERFLOW from a later call, at the latest gk_sync).
+ *  - Synchronisation.  gk_sync first, as gk_ranks_keyed; the call then
+ *    synchronises for the verdict of the sample check and for the flush.  After
+ *    that the rank kernel and the ingest are only ENQUEUED and the call returns
+ *    as gk_ingest does: lo / hi / n / out are ordered on `stream`, and the
+ *    caller keeps ids, xs and the outputs alive and unchanged until the set's
+ *    next call or gk_sync.  A stream the ingest defers is re-run from buffers
+ *    the set owns, never from the caller's.
+ *  - Scratch (GPU engine): exactly gk_ranks_keyed's, at most 40.25 bytes per
+ *    sample and the same per-set part -- no second grouped-batch buffer: the
+ *    8 bytes per sample of index payload, dead once the group-by has read
+ *    them, take the grouped values the ingest reads, the 8 bytes "grouped" hold
+ *    the grouped indices.  GK_E_NOMEM is returned before anything is mutated.
+ *  - GK_RANKK_CHUNK is honoured as by gk_ranks_keyed; answers and states do
+ *    not depend on it. */
+int gk_rank_ingest_keyed(gk_set* set, const int32_t* ids, const double* xs, int64_t count,
+                         int64_t* lo, int64_t* hi, int64_t* n,
+                         const double* qs, int nq, double* out, int mode, void* stream);
 
 /* GKArray.merge(other) (gk:111-154), stream by stream, as the left fold
  * dst.merge(srcs[0]); dst.merge(srcs[1]); ...  Like the reference it mutates

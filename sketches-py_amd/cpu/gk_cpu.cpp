@@ -106,6 +106,8 @@ struct gk_set {
   // gk_ingest_keyed: the grouped batch (only grows)
   std::vector<double> key_vals;
   std::vector<int64_t> key_offs;
+  // gk_rank_ingest_keyed: the sample index of every grouped position (only grows)
+  std::vector<int64_t> key_idx;
 };
 
 namespace {
@@ -780,6 +782,72 @@ int gk_ranks_keyed(gk_set* h, const int32_t* ids, const double* xs, int64_t coun
     if (n) n[k] = cnt;
   });
   return GK_OK;
+}
+
+// gk_ranks_keyed, then gk_ingest_keyed, on ONE group-by: the samples are
+// grouped by id once, with their values and their indices; each occurring
+// stream is flushed and answers its run from the grouped order; the grouped
+// values are then the batch the ingest takes.
+int gk_rank_ingest_keyed(gk_set* h, const int32_t* ids, const double* xs, int64_t count, int64_t* lo, int64_t* hi,
+                         int64_t* n, const double* qs, int nq, double* out, int mode, void* stream) {
+  int rc = check_set(h);
+  if (!rc) rc = check_rank_ingest_keyed_args(ids, xs, count);
+  if (!rc) rc = check_query_args(qs, nq, out, mode);
+  if (rc) return rc;
+  for (int64_t k = 0; k < count; ++k)
+    if (ids[k] >= h->S || (ids[k] >= 0 && std::isnan(xs[k]))) return fail_rank_keyed_sample(k, ids[k], h->S);
+  if (count == 0) return gk_ingest_keyed(h, ids, xs, 0, qs, nq, out, mode, stream);
+  if (h->S == 0) {  // (every id is negative)
+    for (int64_t* o : {lo, hi, n})
+      if (o) std::fill(o, o + count, (int64_t)0);
+    return GK_OK;
+  }
+  try {
+    if ((int64_t)h->key_vals.size() < count) h->key_vals.resize((size_t)count);
+    if ((int64_t)h->key_idx.size() < count) h->key_idx.resize((size_t)count);
+    h->key_offs.resize((size_t)h->S + 1);
+  } catch (...) {
+    return fail(GK_E_NOMEM, "grouped batch of %lld samples failed", (long long)count);
+  }
+  // group_impl's counting sort, carrying the sample index beside the value
+  double* const gv = h->key_vals.data();
+  int64_t* const gi = h->key_idx.data();
+  int64_t* const offs = h->key_offs.data();
+  const int64_t S = h->S;
+  std::fill(offs, offs + S + 1, (int64_t)0);
+  for (int64_t i = 0; i < count; ++i)
+    if (ids[i] >= 0) ++offs[ids[i] + 1];
+  for (int64_t s = 0; s < S; ++s) offs[s + 1] += offs[s];
+  for (int64_t i = 0; i < count; ++i) {
+    if (ids[i] < 0) continue;
+    const int64_t p = offs[ids[i]]++;
+    gv[p] = xs[i];
+    gi[p] = i;
+  }
+  for (int64_t s = S; s > 0; --s) offs[s] = offs[s - 1];
+  offs[0] = 0;
+  // every sample is ranked before any value of the batch is added
+  parallel_for(S, h->threads, [&](int64_t s) {
+    if (offs[s] == offs[s + 1]) return;
+    if (!lo && !hi && !n) return;  // (no rank output: gk_ingest_keyed, no flush)
+    Stream& st = h->st[s];
+    if (st.n > 0) flush_if_pending(h, st);  // gk:166-167
+    for (int64_t p = offs[s]; p < offs[s + 1]; ++p) {
+      int64_t l = 0, u = 0;
+      rank_row(st, gv + p, 1, &l, &u);
+      if (lo) lo[gi[p]] = l;
+      if (hi) hi[gi[p]] = u;
+      if (n) n[gi[p]] = st.n;
+    }
+  });
+  for (int64_t k = 0; k < count; ++k) {
+    if (ids[k] >= 0) continue;  // "no stream": the answer of an empty sketch
+    if (lo) lo[k] = 0;
+    if (hi) hi[k] = 0;
+    if (n) n[k] = 0;
+  }
+  if (nq == 0) return gk_ingest(h, gv, offs, stream);
+  return gk_ingest_quantiles(h, gv, offs, qs, nq, out, mode, stream);
 }
 
 int gk_merge(gk_set* dst, gk_set* const* srcs, int nsrcs, void* stream) {

@@ -160,7 +160,11 @@ struct gk_set {
   int32_t* d_sel = nullptr;
   int64_t sel_words = 0;
   // gk_ranks_keyed: the sample indices the group-by carries as its payload
-  // (rk_idx_cap doubles, bit-cast int64; made on first use, only grown)
+  // (rk_idx_cap doubles, bit-cast int64; made on first use, only grown).
+  // gk_rank_ingest_keyed: the same, and once the group-by has consumed them the
+  // buffer takes the grouped VALUES its ingest reads (k_rank_ingest_keyed) --
+  // h->last.x of that call, with kg_offs as h->last.offs: like kg_vals it is
+  // rewritten only by calls that have settled the last one (gk_sync first).
   double* rk_idx = nullptr;
   int64_t rk_idx_cap = 0;
   // What the call in progress still has to join on the caller's stream: set
@@ -1644,19 +1648,18 @@ static int rank_keyed_chunk(int* chunk) {
   return GK_OK;
 }
 
-int gk_ranks_keyed(gk_set* h, const int32_t* ids, const double* xs, int64_t count, int64_t* lo, int64_t* hi, int64_t* n,
-                   void* stream) {
-  int chunk = 0;
-  int rc = check_set(h);
-  if (!rc) rc = check_rank_keyed_args(ids, xs, count, lo, hi, n);
-  if (!rc) rc = rank_keyed_chunk(&chunk);
-  if (!rc) rc = gk_sync(h, stream);
-  if (rc || count == 0) return rc;
-  hipStream_t s = (hipStream_t)stream;
+// The head of gk_ranks_keyed and gk_rank_ingest_keyed, after their argument
+// checks and gk_sync (count > 0): the scratch, the check kernel and its verdict,
+// the flush of the occurring streams (*nflush of them; none when S == 0 or
+// when the caller wants no rank: `flush` false).
+static int rank_keyed_begin(gk_set* h, const int32_t* ids, const double* xs, int64_t count, bool flush, hipStream_t s,
+                            int64_t* nflush) {
+  *nflush = 0;
   // every scratch before the first launch: GK_E_NOMEM mutates nothing.  (The
   // stream is idle after gk_sync and an in-flight keyed ingest is settled:
-  // its grouped batch in kg_vals / kg_offs is free.)
-  rc = ensure_group_scratch(h, count, true, s);
+  // its grouped batch in kg_vals / kg_offs -- rk_idx / kg_offs after a
+  // gk_rank_ingest_keyed -- is free.)
+  int rc = ensure_group_scratch(h, count, true, s);
   if (!rc && count > h->rk_idx_cap) {
     h->rk_idx_cap = 0;
     if (!renew_dev(&h->rk_idx, (size_t)count * sizeof(double)))
@@ -1681,18 +1684,69 @@ int gk_ranks_keyed(gk_set* h, const int32_t* ids, const double* xs, int64_t coun
     HIP_TRY(hipMemcpy(&id, ids + first, sizeof(int32_t), hipMemcpyDeviceToHost));
     return fail_rank_keyed_sample(first, id, h->S);
   }
-  if (h->S == 0) {  // (every id is negative)
-    for (int64_t* o : {lo, hi, n})
-      if (o) HIP_TRY(hipMemsetAsync(o, 0, (size_t)count * sizeof(int64_t), s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return GK_OK;
-  }
-  rc = flush_listed(h, list, h->h_ovf[GK_SEL_COUNT], s);
-  if (rc) return rc;  // (GK_E_OVERFLOW: no output is written)
+  if (h->S == 0 || !flush) return GK_OK;  // (S == 0: every id is negative)
+  *nflush = h->h_ovf[GK_SEL_COUNT];
+  return flush_listed(h, list, *nflush, s);  // (GK_E_OVERFLOW: no output is written)
+}
+
+// S == 0: every id is negative, every row (0, 0, 0)
+static int rank_keyed_zero_rows(int64_t* lo, int64_t* hi, int64_t* n, int64_t count, hipStream_t s) {
+  for (int64_t* o : {lo, hi, n})
+    if (o) HIP_TRY(hipMemsetAsync(o, 0, (size_t)count * sizeof(int64_t), s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return GK_OK;
+}
+
+int gk_ranks_keyed(gk_set* h, const int32_t* ids, const double* xs, int64_t count, int64_t* lo, int64_t* hi, int64_t* n,
+                   void* stream) {
+  int chunk = 0;
+  int rc = check_set(h);
+  if (!rc) rc = check_rank_keyed_args(ids, xs, count, lo, hi, n);
+  if (!rc) rc = rank_keyed_chunk(&chunk);
+  if (!rc) rc = gk_sync(h, stream);
+  if (rc || count == 0) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  int64_t nflush = 0;
+  rc = rank_keyed_begin(h, ids, xs, count, true, s, &nflush);
+  if (rc) return rc;
+  if (h->S == 0) return rank_keyed_zero_rows(lo, hi, n, count, s);
   // the stable group-by of the samples by id, payload = sample index
   HIP_TRY(gk_launch_group_by_key(h->kg, ids, h->rk_idx, count, h->S, h->kg_vals, h->kg_offs, s));
   HIP_TRY(gk_launch_rank_keyed(h->st, ids, xs, count, h->kg_vals, h->kg_offs, chunk, lo, hi, n, s));
   return select_end(h, s);
+}
+
+// ---- keyed score-and-ingest: gk_ranks_keyed, then gk_ingest_keyed, one group-by
+
+int gk_rank_ingest_keyed(gk_set* h, const int32_t* ids, const double* xs, int64_t count, int64_t* lo, int64_t* hi,
+                         int64_t* n, const double* qs, int nq, double* out, int mode, void* stream) {
+  int chunk = 0;
+  int rc = check_set(h);
+  if (!rc) rc = check_rank_ingest_keyed_args(ids, xs, count);
+  if (!rc) rc = check_query_args(qs, nq, out, mode);
+  if (!rc) rc = rank_keyed_chunk(&chunk);
+  if (!rc) rc = gk_sync(h, stream);
+  if (rc) return rc;
+  if (count == 0) return gk_ingest_keyed(h, ids, xs, 0, qs, nq, out, mode, stream);
+  hipStream_t s = (hipStream_t)stream;
+  int64_t nflush = 0;
+  // (no rank output: gk_ingest_keyed behind the sample check -- no rank, no flush)
+  rc = rank_keyed_begin(h, ids, xs, count, lo || hi || n, s, &nflush);
+  if (rc) return rc;
+  if (h->S == 0) return rank_keyed_zero_rows(lo, hi, n, count, s);
+  // what gk_ranks_keyed ends with, ahead of the ingest: the flush may have
+  // promoted streams, and the ingest's grow_pools reads the slots in use
+  if (nflush > 0) {
+    rc = select_end(h, s);
+    if (rc) return rc;
+  }
+  // ONE group-by, payload = sample index; k_rank_ingest_keyed then turns the
+  // consumed payload buffer into the grouped values: (rk_idx, kg_offs) is the
+  // batch gk_ingest_keyed's own group-by would have made.  Only enqueued from here.
+  HIP_TRY(gk_launch_group_by_key(h->kg, ids, h->rk_idx, count, h->S, h->kg_vals, h->kg_offs, s));
+  HIP_TRY(gk_launch_rank_ingest_keyed(h->st, ids, xs, count, h->kg_vals, h->kg_offs, chunk, lo, hi, n, h->rk_idx, s));
+  if (nq == 0) return gk_ingest(h, h->rk_idx, h->kg_offs, stream);
+  return gk_ingest_quantiles(h, h->rk_idx, h->kg_offs, qs, nq, out, mode, stream);
 }
 
 static int merge_self(gk_set* dst, hipStream_t s, void* stream);

@@ -74,6 +74,14 @@ int check_rank_keyed_args(const int32_t* ids, const double* xs, int64_t count, c
   return GK_OK;
 }
 
+// gk_rank_ingest_keyed: the same, but lo, hi and n may all be NULL
+int check_rank_ingest_keyed_args(const int32_t* ids, const double* xs, int64_t count) {
+  int rc = check_count(count);
+  if (rc) return rc;
+  if (count > 0 && (!ids || !xs)) return fail(GK_E_ARG, "ids or xs is null");
+  return GK_OK;
+}
+
 // the first offending sample of gk_ranks_keyed: its id if that is >= S, else its NaN
 int fail_rank_keyed_sample(int64_t index, int32_t id, int64_t S) {
   if (id >= S)

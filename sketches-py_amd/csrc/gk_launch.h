@@ -322,6 +322,15 @@ hipError_t gk_launch_rank_keyed_check(const GKState& st, const int32_t* ids, con
 hipError_t gk_launch_rank_keyed(const GKState& st, const int32_t* ids, const double* xs, int64_t count,
                                 const double* gidx, const int64_t* goffs, int chunk, int64_t* lo, int64_t* hi,
                                 int64_t* n, hipStream_t stream);
+// ---- keyed score-and-ingest (gk_rankingest.hip) ----
+// k_rank_ingest_keyed: k_rank_keyed, and gvals[p] = xs[gidx[p]] (bit for bit)
+// for every grouped position p < goffs[S] -- the grouped values, in arrival
+// order per stream: (gvals, goffs) is the CSR batch of the samples.  gvals has
+// room for `count` doubles and is none of the other buffers.  lo, hi and n may
+// all be NULL: only gvals is written then.
+hipError_t gk_launch_rank_ingest_keyed(const GKState& st, const int32_t* ids, const double* xs, int64_t count,
+                                       const double* gidx, const int64_t* goffs, int chunk, int64_t* lo, int64_t* hi,
+                                       int64_t* n, double* gvals, hipStream_t stream);
 // ---- key directory (gk_dir.hip): int64 keys -> int32 ids, a device hash table ----
 // Exclusive scan in place of n uint32 values whose sum stays below 2^32 (the
 // same k_scan_* kernels); *total_out (device, may be NULL) = the sum.  skip

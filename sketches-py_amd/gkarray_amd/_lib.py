@@ -67,6 +67,7 @@ SYMBOLS = {
     "gk_ranks": (_INT, [_P, ctypes.POINTER(_D), _INT, _P, _P, _P]),
     "gk_ranks_select": (_INT, [_P, _P, _I64, ctypes.POINTER(_D), _INT, _P, _P, _P]),
     "gk_ranks_keyed": (_INT, [_P, _P, _P, _I64, _P, _P, _P, _P]),
+    "gk_rank_ingest_keyed": (_INT, [_P, _P, _P, _I64, _P, _P, _P, ctypes.POINTER(_D), _INT, _P, _INT, _P]),
     "gk_merge": (_INT, [_P, ctypes.POINTER(_P), _INT, _P]),
     "gk_rollup": (_INT, [_P, _P, _P, _P, _P]),
     "gk_merge_compress": (_INT, [_P, _P, _P, _P, _P, _P]),

@@ -307,11 +307,32 @@ class KeyedStreamSet:
         """Where each sample sits in the distribution of its own key: float64
         [len(keys)], ``StreamSet.cdf_keyed`` -- ``(lo + hi) / (2 n)``, NaN for
         an unknown key, ``NO_KEY`` or an empty sketch.  Scoring a batch against
-        the history BEFORE it joins it is ``s = k.score(keys, v); k.add(keys,
-        v)``.  Like ``quantiles``, ``score`` flushes the pending values of the
-        streams it touches."""
+        the history BEFORE it joins it is ``score_add(keys, v)``, one call
+        with the answers of ``s = k.score(keys, v); k.add(keys, v)``.  Like
+        ``quantiles``, ``score`` flushes the pending values of the streams it
+        touches."""
         ids, v = self._sample_args(keys, values)
         return self.streams.cdf_keyed(ids, v)
+
+    def score_add(self, keys, values, quantiles=None, single=False):
+        """``s = score(keys, values); add(keys, values)`` in one call
+        (``gk_dir_assign`` + ``gk_rank_ingest_keyed``): every sample is scored
+        against its key's history before any value of the batch joins it, then
+        the batch is added.  A key that is new in this batch is bound first;
+        its history is empty, so every one of its samples in the batch scores
+        NaN.  ``NO_KEY`` samples score NaN and are skipped.  A NaN value on a
+        sample with a key raises ``GKBackendError`` (GK_E_ARG); the new keys of
+        that batch stay bound, with empty sketches.  Returns the scores, float64
+        [len(keys)], or ``(scores, q)`` with ``quantiles`` -- ``q`` as ``add``
+        returns it.  The ``max_streams`` refusal leaves the object unchanged,
+        as in ``add``."""
+        k = self.directory._keys(keys)
+        v = values if isinstance(values, torch.Tensor) else torch.as_tensor(values, dtype=torch.float64)
+        if v.dim() != 1 or v.numel() != k.numel():
+            raise ValueError("keys and values must be one-dimensional and of one length")
+        ids = self._assign_growing(k)
+        out = self.streams.score_ingest_keyed(ids, v, quantiles=quantiles, single=single)
+        return out if quantiles is None else (out[0], out[1][:self.directory.bound])
 
     def stats(self, keys):
         return self.streams.stats_select(self._ids(keys))

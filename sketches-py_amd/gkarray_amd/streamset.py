@@ -520,6 +520,57 @@ class StreamSet:
         lo, hi, n = self.ranks_keyed(ids, xs, n=True)
         return (lo + hi).to(torch.float64) / (2.0 * n.to(torch.float64))
 
+    # ------------------------------------------------- keyed score-and-ingest
+    def rank_ingest_keyed(self, ids, values, lo=True, hi=True, n=False, quantiles=None, single=False, sync=True):
+        """``ranks_keyed(ids, values, lo, hi, n)`` followed by
+        ``ingest_keyed(ids, values, quantiles, single, sync)`` in one call
+        (``gk_rank_ingest_keyed``): every sample is ranked against its stream
+        BEFORE any value of the batch is added, then the batch is added in
+        arrival order -- answers and stream states are bit for bit those of
+        the two calls, at one group-by of the samples instead of two.  Returns
+        ``(lo, hi, n)``, or ``(lo, hi, n, q)`` with ``quantiles``; outputs as
+        ``ranks_keyed`` (all three may be left out: the call is then
+        ``ingest_keyed``), ``q``, ``single`` and ``sync`` as ``ingest_keyed``.
+        A negative id is "no stream": row (0, 0, 0), value not added.  An
+        id >= num_streams or a NaN value on a live row raises
+        ``GKBackendError`` (GK_E_ARG) from the call itself with nothing changed,
+        so NaN cannot be added this way.  With ``sync=False`` the outputs are
+        ordered on the current HIP stream."""
+        # (a Python list goes straight to float64, as in ranks_keyed)
+        v = values if isinstance(values, torch.Tensor) else torch.as_tensor(values, dtype=torch.float64)
+        i, v = self._keyed_args(ids, v)
+        K = i.numel()
+        lo_t, lo_p = self._keyed_out(lo, K, "lo")
+        hi_t, hi_p = self._keyed_out(hi, K, "hi")
+        n_t, n_p = self._keyed_out(n, K, "n")
+        pi, pv = (_ptr(i), _ptr(v)) if K else (None, None)
+        if quantiles is None:
+            nq, arr, out = 0, None, None
+        else:
+            qs = [float(q) for q in quantiles]
+            nq = len(qs)
+            out = torch.empty((self.num_streams, max(nq, 1)), dtype=torch.float64, device=self.device)
+            arr = (ctypes.c_double * max(nq, 1))(*qs)
+        mode = L.GK_Q_SINGLE if single else L.GK_Q_LIST
+        with self._ctx():
+            self._check(self._lib.gk_rank_ingest_keyed(self._h, pi, pv, K, _ptr(lo_p), _ptr(hi_p), _ptr(n_p), arr, nq,
+                                                       _ptr(out), mode, self._sp()))
+        self._inflight = (i, v, lo_p, hi_p, n_p, out)
+        if sync:
+            self.sync()
+        if quantiles is None:
+            return lo_t, hi_t, n_t
+        return lo_t, hi_t, n_t, out[:, :nq]
+
+    def score_ingest_keyed(self, ids, values, quantiles=None, single=False, sync=True):
+        """``cdf_keyed(ids, values)`` -- ``(lo + hi) / (2 n)`` against the state
+        before the batch, NaN where n == 0 -- and then ``ingest_keyed``, through
+        ``rank_ingest_keyed``.  Returns the scores, or ``(scores, q)`` with
+        ``quantiles``."""
+        r = self.rank_ingest_keyed(ids, values, n=True, quantiles=quantiles, single=single, sync=sync)
+        score = (r[0] + r[1]).to(torch.float64) / (2.0 * r[2].to(torch.float64))
+        return score if quantiles is None else (score, r[3])
+
     # ------------------------------------------------------------------ export
     def tables(self):
         """All tables in CSR form: (offs int64[S+1], v f64, g i32, d i32)."""
