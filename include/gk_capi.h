@@ -28,7 +28,8 @@
  *    gk_merge, gk_rollup, gk_quantiles_select, gk_flush_select,
  *    gk_reset_select, gk_stats_select, gk_ranks, gk_ranks_select,
  *    gk_ranks_keyed, gk_merge_compress, gk_import, gk_save / gk_load, gk_pack_select_bytes,
- *    gk_pack_select, gk_unpack_select and gk_num_promoted synchronise before
+ *    gk_pack_select, gk_unpack_select, gk_compact, gk_class_usage and
+ *    gk_num_promoted synchronise before
  *    returning; so do the key directory's calls (gk_dir_*, an object of its
  *    own).  gk_rank_ingest_keyed synchronises for its rank half's checks and
  *    flush and then only enqueues (see there).
@@ -220,8 +221,8 @@ int gk_stats(gk_set* set, int64_t* n, double* mn, double* mx, double* sum,
  *   empty table, no pending values, n = 0, min = +inf, max = -inf, sum = avg
  *   = 0.  On the GPU engine a reset stream KEEPS its capacity class and slot
  *   (arenas are bump-allocated and the class member lists have no removal):
- *   memory is not returned and gk_num_promoted does not drop.  gk_reset is the
- *   call that gives everything back.
+ *   memory is not returned and gk_num_promoted does not drop until gk_compact
+ *   re-places the streams; gk_reset gives everything back at once.
  * gk_stats_select: gk_stats' seven arrays gathered at ids into outputs of
  *   length `count`; any output pointer may be NULL.  Does not flush.
  *  - Scratch (GPU engine; owned by the set, only grows, freed by gk_destroy):
@@ -561,7 +562,7 @@ int gk_fold_packed(gk_set* dst, const void* const* bufs, int nbufs, void* stream
  *    - Unlisted streams stay bit-identical, including class and slot.
  *    - Capacity class (GPU engine).  A listed stream whose new table fits its
  *      class keeps class and slot; it is never demoted (gk_reset_select's
- *      reasons); one whose table does not fit moves up to the first class
+ *      reasons; gk_compact is the call that demotes); one whose table does not fit moves up to the first class
  *      that holds it, and gk_num_promoted may rise.
  *    - GK_E_NOMEM while growing a class arena is returned before the first
  *      write: every listed stream then holds its complete old state.  At any
@@ -574,6 +575,86 @@ int gk_fold_packed(gk_set* dst, const void* const* bufs, int nbufs, void* stream
 int gk_pack_select_bytes(gk_set* set, const int32_t* ids, int64_t count, int64_t* bytes, void* stream);
 int gk_pack_select(gk_set* set, const int32_t* ids, int64_t count, void* buf, int64_t bytes, void* stream);
 int gk_unpack_select(gk_set* set, const int32_t* ids, int64_t count, const void* buf, void* stream);
+
+/* ---- compaction: streams back into the smallest capacity class that holds them --
+ * What the reference's user gets for free when a key is dropped and its
+ * GKArray collected: the memory.  On the GPU engine classes only grow (an
+ * ingest, gk_unpack_select, a merge move a stream up; gk_reset_select and
+ * gk_unpack_select never move one down), so a set that churns streams -- a
+ * KeyedStreamSet whose removed keys' ids are recycled -- ratchets its promoted
+ * population, its member lists and its arenas upwards.  gk_compact re-places
+ * every stream; gk_class_usage shows what a set holds per class.  Nothing calls
+ * gk_compact implicitly: when to compact is the caller's decision.
+ *
+ * gk_compact
+ *  - Synchronisation.  gk_sync first (deferred streams of the previous call are
+ *    re-run, a sticky error of it is returned instead of doing the work: nothing
+ *    is compacted then, and the outputs are not written); the call synchronises
+ *    before returning.
+ *  - Placement.  A stream whose table has E entries fits class t when
+ *    E <= capacity(t) - 1 (gk_unpack_select's rule).  With fit(E) the smallest
+ *    such class, the stream's class after the call is min(old class, fit(E)):
+ *    compaction never promotes.  Pending values live beside the tables and
+ *    play no part.
+ *  - State.  Every stream's table, pending values in insertion order and
+ *    n/_min/_max/_sum/_avg are bit-identical before and after, and every later
+ *    call (ingest, flush, quantiles, ranks, merge, roll-up, pack) answers with
+ *    the bits it would have given without the compaction.  Only class, slot,
+ *    member lists and arena sizes change.
+ *  - Bookkeeping (GPU engine).  Afterwards the member list of every class c > 0
+ *    holds exactly the streams of class c, each once, in unspecified order; the
+ *    slots of those streams are a permutation of [0, slots_used) and slots_used
+ *    equals their number; and an ingest into a set with no promoted stream
+ *    takes the path of a fresh set again.
+ *  - Arenas.  Class c > 0 keeps min(slots_alloc, min(S, max(the slots a new set
+ *    starts the class with, 2 * slots_used))) slots -- twice what is in use, so
+ *    that the next call does not regrow an arena no stream has entered -- or
+ *    slots_used if the streams that came down into c need more than that.  A
+ *    class left at 0 slots (the classes beyond 32768 entries, which a new set
+ *    allocates on first use) returns its arena AND its workspace: it is the
+ *    not-yet-used class of gk_create again.  A class that keeps slots keeps its
+ *    workspace: the device moves streams into such a class in the middle of a
+ *    call, with no host step that could allocate one.  A class in which nothing
+ *    changes (no stream leaves or enters, slots dense, size at target) is not
+ *    copied.
+ *  - *demoted (may be NULL): streams whose class dropped.  *bytes_freed (may be
+ *    NULL): arena plus workspace bytes before the call minus those after it,
+ *    >= 0 unless arrivals made an arena grow; exactly what summing
+ *    gk_class_usage over the classes before and after gives.
+ *  - GK_E_NOMEM.  HIP has no realloc: a class's new arena is allocated beside
+ *    the old ones.  The work goes by destination class ascending and the old
+ *    arena of a class is freed as soon as that class is done, so the peak
+ *    extra memory is ONE new arena (at most the size of the old one of that
+ *    class, or of its arrivals).  On failure the classes below the failing one
+ *    are compacted, the others are as before; every stream holds its complete
+ *    state bit for bit -- header and table of one placement, never of two --
+ *    and the set stays fully usable.  *demoted then counts the streams the plan
+ *    found, moved or not.
+ *  - S == 0 and a set with nothing promoted return GK_OK with *demoted =
+ *    *bytes_freed = 0 and touch nothing; so does a second gk_compact straight
+ *    after one.
+ *  - Scratch (GPU engine; the selection scratch, owned by the set, only grows,
+ *    freed by gk_destroy): 64 bytes of counters.  Its GK_E_NOMEM is returned
+ *    before anything is mutated.
+ *  - Host engine: one unbounded class, nothing to demote; the call returns the
+ *    unused capacity of every stream's table and pending vectors
+ *    (shrink_to_fit).  *demoted = 0, *bytes_freed = capacity bytes before minus
+ *    after.
+ *
+ * gk_class_usage: one capacity class of the set, after settling the set as
+ *   gk_num_promoted does (deferred streams are placed first; a sticky error is
+ *   left for the next call that reports one).  cls outside [0, number of
+ *   classes) is GK_E_ARG (the host engine has class 0 only); any output
+ *   pointer may be NULL.  *streams: the streams whose class is cls -- summed
+ *   over the classes S, over cls > 0 gk_num_promoted.  *slots_used,
+ *   *slots_alloc: slots handed out and allocated in the class's arena (class
+ *   0: both S).  *arena_bytes = slots_alloc * capacity * 16 (host engine: the
+ *   summed capacities of the streams' table and pending vectors in bytes).
+ *   *workspace_bytes: the class's global workspace, 0 when it has none. */
+int gk_compact(gk_set* set, int64_t* demoted, int64_t* bytes_freed, void* stream);
+int gk_class_usage(gk_set* set, int cls, int64_t* streams, int64_t* slots_used,
+                   int64_t* slots_alloc, int64_t* arena_bytes, int64_t* workspace_bytes,
+                   void* stream);
 
 /* ---- key directory: int64 keys to stream ids, assigned by the engine ---------
  * The dict of the reference's user (sketches[key] = GKArray(eps) on a key

@@ -11,6 +11,9 @@
  *    bound, any finite eps > 0 is accepted, GK_E_OVERFLOW never occurs
  *    (gk_unpack_select included: a table of any size is installed) -- except
  *    from gk_dir_assign, whose capacity rule is the same in both engines;
+ *    gk_class_usage knows class 0 alone (its arena_bytes: the summed capacities
+ *    of the streams' table and pending vectors), and gk_compact demotes
+ *    nothing: it returns those vectors' unused capacity (shrink_to_fit);
  *  - streams are processed in parallel on host threads (each stream strictly
  *    in insertion order): GK_CPU_THREADS (environment) or gk_cpu_set_threads,
  *    default = the CPUs this process may run on.

@@ -1222,6 +1222,47 @@ int gk_unpack_select(gk_set* h, const int32_t* ids, int64_t count, const void* b
   return GK_OK;
 }
 
+// ---- compaction: one unbounded class, so only unused vector capacity goes back
+static int64_t capacity_bytes(const gk_set* h) {
+  int64_t b = 0;
+  for (const Stream& st : h->st)
+    b += (int64_t)(st.tab.capacity() * sizeof(Rec)) + (int64_t)(st.pend.capacity() * sizeof(double));
+  return b;
+}
+
+int gk_compact(gk_set* h, int64_t* demoted, int64_t* bytes_freed, void* stream) {
+  (void)stream;
+  int rc = check_set(h);
+  if (rc) return rc;
+  const int64_t before = capacity_bytes(h);
+  // (a shrink that finds no memory for the smaller copy keeps the vector as it is)
+  parallel_for(h->S, h->threads, [&](int64_t s) {
+    Stream& st = h->st[(size_t)s];
+    try {
+      st.tab.shrink_to_fit();
+      st.pend.shrink_to_fit();
+    } catch (...) {
+    }
+  });
+  if (demoted) *demoted = 0;
+  if (bytes_freed) *bytes_freed = before - capacity_bytes(h);
+  return GK_OK;
+}
+
+int gk_class_usage(gk_set* h, int cls, int64_t* streams, int64_t* slots_used, int64_t* slots_alloc,
+                   int64_t* arena_bytes, int64_t* workspace_bytes, void* stream) {
+  (void)stream;
+  int rc = check_set(h);
+  if (rc) return rc;
+  if (cls != 0) return fail(GK_E_ARG, "class %d outside [0, 1)", cls);
+  if (streams) *streams = h->S;
+  if (slots_used) *slots_used = h->S;
+  if (slots_alloc) *slots_alloc = h->S;
+  if (arena_bytes) *arena_bytes = capacity_bytes(h);
+  if (workspace_bytes) *workspace_bytes = 0;
+  return GK_OK;
+}
+
 // ---- key directory: the loop of gk_capi.h over an open-addressing table -------
 }  // extern "C"
 

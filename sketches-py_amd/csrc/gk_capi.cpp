@@ -284,6 +284,94 @@ int grow_class(gk_set* h, int c, int64_t want, hipStream_t s) {
   return GK_OK;
 }
 
+// gk_compact: the slots class c > 0 keeps for `members` streams -- what a set
+// would start with (initial_slots) or twice the members, so that the next
+// call's grow_pools (2 * used > alloc) does not regrow an arena no stream has
+// entered; never more than it has, unless the streams that come down into it
+// need more.
+int64_t compact_slots(const gk_set* h, int c, int64_t members) {
+  int64_t want = std::min<int64_t>(std::max<int64_t>(h->S, 1), std::max<int64_t>(initial_slots(h, c), 2 * members));
+  want = std::min<int64_t>(want, h->st.alloc[c]);
+  return std::max<int64_t>(want, members);
+}
+
+// Bytes of class c's arena and of its workspace (gk_class_usage).
+int64_t arena_bytes(const gk_set* h, int c) {
+  return (c == 0 ? h->S : (int64_t)h->st.alloc[c]) * h->st.cap[c] * (int64_t)sizeof(GKRec);
+}
+int64_t workspace_bytes(const gk_set* h, int c) {
+  return h->d_ws[c] ? (int64_t)h->ws_bytes[c] * h->ws_blocks[c] : 0;
+}
+
+// The device and arena work of gk_compact on a settled, synchronised set; ctl:
+// GK_CMP_WORDS words of device scratch.  Destination classes ascending: class
+// 0 first (the streams that go home, no allocation), then each class t > 0
+// gets a new arena beside the old ones, its members -- the ones that stay and
+// the ones that come down from the classes above, whose old arenas are all
+// still there -- move into dense slots of it, and the old arena of t, which no
+// stream lives in any more, is freed before class t + 1 is looked at: one new
+// arena at a time.  GK_E_NOMEM leaves the classes below t compacted and every
+// stream of t and above where it was, header and table together.
+int compact_classes(gk_set* h, int32_t* ctl, hipStream_t s, int64_t* demoted) {
+  GKState& st = h->st;
+  const int R = st.nclass;
+  int32_t plan[GK_CMP_WORDS], ctr[2 * GK_MAX_CLASSES];
+  static_assert(GK_CTR_LCNT == GK_CTR_USED + GK_MAX_CLASSES, "slots used and list lengths are read back together");
+  HIP_TRY(hipMemsetAsync(ctl, 0, GK_CMP_WORDS * sizeof(int32_t), s));
+  HIP_TRY(gk_launch_compact_plan(st, ctl, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpy(plan, ctl, sizeof(plan), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(ctr, h->d_ctr + GK_CTR_USED, sizeof(ctr), hipMemcpyDeviceToHost));
+  int64_t home = 0;  // streams that go back to class 0
+  for (int c = 1; c < R; ++c) {
+    *demoted += plan[GK_CMP_LEAVE + c];
+    home += plan[GK_CMP_LEAVE + c] - plan[GK_CMP_ARRIVE + c];
+  }
+  if (home > 0) HIP_TRY(gk_launch_compact_move(st, 0, nullptr, 0, nullptr, ctl, s));
+  int64_t promoted = 0;
+  for (int t = 1; t < R; ++t) {
+    const int32_t members = plan[GK_CMP_FINAL + t];
+    const int64_t want = compact_slots(h, t, members);
+    promoted += members;
+    // nothing leaves or enters, slots and list already dense, arena at its size: not copied
+    if (plan[GK_CMP_LEAVE + t] == 0 && plan[GK_CMP_ARRIVE + t] == 0 && ctr[t] == members &&
+        ctr[GK_MAX_CLASSES + t] == members && want == st.alloc[t])
+      continue;
+    GKRec* nt = nullptr;
+    // (streams may come down into a class that had no slots yet: slots > 0 implies a workspace)
+    if (want > 0 && ensure_ws(h, t) != GK_OK) {
+      (void)hipStreamSynchronize(s);
+      return GK_E_NOMEM;
+    }
+    if (want > 0 && hipMalloc(&nt, (size_t)want * st.cap[t] * sizeof(GKRec)) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipStreamSynchronize(s);
+      return fail(GK_E_NOMEM, "compaction: class-%d arena of %lld slots failed (classes below it are compacted)", t,
+                  (long long)want);
+    }
+    if (members > 0) HIP_TRY(gk_launch_compact_move(st, t, nt, want, h->d_list[t], ctl, s));
+    const int32_t cnt[2] = {members, members};
+    HIP_TRY(hipMemcpyAsync(h->d_ctr + GK_CTR_USED + t, &cnt[0], sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->d_ctr + GK_CTR_LCNT + t, &cnt[1], sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));  // (cnt is read; the old arena is read no more)
+    if (st.tab[t]) (void)hipFree(st.tab[t]);
+    st.tab[t] = nt;
+    st.alloc[t] = (int32_t)want;
+    // a class back at no slots is the not-yet-used class of gk_create: no workspace either
+    // (grow_class makes both again when a stream is deferred for want of a slot)
+    if (want == 0 && h->d_ws[t]) {
+      (void)hipFree(h->d_ws[t]);
+      h->d_ws[t] = nullptr;
+      h->ws_bytes[t] = 0;
+      h->ws_blocks[t] = 0;
+    }
+  }
+  HIP_TRY(hipMemcpy(plan, ctl, sizeof(plan), hipMemcpyDeviceToHost));
+  if (plan[GK_CMP_STUCK] != 0) return fail(GK_E_HIP, "compaction: %d stream(s) found no slot", plan[GK_CMP_STUCK]);
+  h->no_members = promoted == 0;
+  return GK_OK;
+}
+
 // Consume the counters read back at the end of the last call: report streams
 // that found no class / slot (sticky GK_E_OVERFLOW), learn the presort
 // workspace the last call needed.  block: wait for that call to finish.
@@ -2336,6 +2424,55 @@ int gk_unpack_select(gk_set* h, const int32_t* ids, int64_t count, const void* b
   if (rc) return rc;
   if (h->h_ovf[0] != 0)
     return fail(GK_E_OVERFLOW, "%d packed stream(s) found no slot in a capacity class and keep their state", h->h_ovf[0]);
+  return GK_OK;
+}
+
+// ---- compaction (gk_compact.hip) ------------------------------------------------
+int gk_compact(gk_set* h, int64_t* demoted, int64_t* bytes_freed, void* stream) {
+  int rc = check_set(h);
+  if (!rc) rc = gk_sync(h, stream);
+  if (rc) return rc;
+  if (demoted) *demoted = 0;
+  if (bytes_freed) *bytes_freed = 0;
+  if (h->S == 0 || h->no_members) return GK_OK;  // nothing promoted: nothing to place
+  hipStream_t s = (hipStream_t)stream;
+  rc = ensure_select_words(h, GK_CMP_WORDS);  // (before anything is mutated)
+  if (rc) return rc;
+  int64_t before = 0, after = 0, dem = 0;
+  for (int c = 0; c < h->st.nclass; ++c) before += arena_bytes(h, c) + workspace_bytes(h, c);
+  rc = compact_classes(h, h->d_sel, s, &dem);
+  // (also after GK_E_NOMEM: the classes done so far have new counters)
+  const int re = select_end(h, s);
+  for (int c = 0; c < h->st.nclass; ++c) after += arena_bytes(h, c) + workspace_bytes(h, c);
+  if (demoted) *demoted = dem;
+  if (bytes_freed) *bytes_freed = before - after;
+  return rc ? rc : re;
+}
+
+int gk_class_usage(gk_set* h, int cls, int64_t* streams, int64_t* slots_used, int64_t* slots_alloc,
+                   int64_t* arena_bytes_out, int64_t* workspace_bytes_out, void* stream) {
+  int rc = check_set(h);
+  if (rc) return rc;
+  if (cls < 0 || cls >= h->st.nclass) return fail(GK_E_ARG, "class %d outside [0, %d)", cls, h->st.nclass);
+  hipStream_t s = (hipStream_t)stream;
+  // settled as gk_num_promoted settles: deferred streams are placed first; a
+  // sticky error stays for the next call that reports one
+  HIP_TRY(hipStreamSynchronize(s));
+  rc = settle(h, s, true);
+  if (rc) return rc;
+  int64_t members = 0;
+  int32_t used = 0;
+  if (h->S > 0) {
+    std::vector<int32_t> c(h->S);
+    HIP_TRY(hipMemcpy(c.data(), h->st.cls, h->S * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int32_t v : c) members += v == cls;
+    if (cls > 0) HIP_TRY(hipMemcpy(&used, h->d_ctr + GK_CTR_USED + cls, sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
+  if (streams) *streams = members;
+  if (slots_used) *slots_used = cls == 0 ? h->S : used;
+  if (slots_alloc) *slots_alloc = cls == 0 ? h->S : h->st.alloc[cls];
+  if (arena_bytes_out) *arena_bytes_out = arena_bytes(h, cls);
+  if (workspace_bytes_out) *workspace_bytes_out = workspace_bytes(h, cls);
   return GK_OK;
 }
 

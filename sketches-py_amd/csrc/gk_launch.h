@@ -435,3 +435,19 @@ static_assert((GK_CTR_CALL * 4) % 64 == 0 && (GK_CALL_BYTES - GK_CTR_CALL * 4) %
 // free slot), -2 -> class cls+1 (import), level >= 0 -> class `level` if below it
 hipError_t gk_launch_promote_dev(const GKState& st, const int32_t* count, const int32_t* list, int level,
                                  const GKPoolDev& pool, hipStream_t stream);
+// ---- compaction (gk_compact.hip): every stream into the smallest class that holds its table ----
+// Control words of a gk_compact call (zeroed by the caller), per class k > 0:
+#define GK_CMP_FINAL 0    // [k] streams whose class after the compaction is k
+#define GK_CMP_LEAVE 4    // [4 + k] streams of class k that move down (the demoted)
+#define GK_CMP_ARRIVE 8   // [8 + k] streams that move down into class k
+#define GK_CMP_TAKEN 12   // [12 + k] slots of the new arena of class k handed out by k_compact_move
+#define GK_CMP_STUCK 12   // (class 0 has no arena counter) streams k_compact_move found no slot for: never
+#define GK_CMP_WORDS 16
+static_assert(GK_CMP_TAKEN + GK_MAX_CLASSES <= GK_CMP_WORDS, "one counter per class");
+// the counts above; mutates no stream state
+hipError_t gk_launch_compact_plan(const GKState& st, int32_t* ctl, hipStream_t stream);
+// the streams above class 0 whose class after the compaction is t move their tables: t == 0 to their class-0
+// home, t > 0 into slots [0, ctl[GK_CMP_TAKEN + t]) of the new arena ntab (nalloc slots; st holds the old
+// arenas) with nlist[slot] = the stream -- the class's rebuilt member list
+hipError_t gk_launch_compact_move(const GKState& st, int t, GKRec* ntab, int64_t nalloc, int32_t* nlist, int32_t* ctl,
+                                  hipStream_t stream);

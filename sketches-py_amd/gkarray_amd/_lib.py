@@ -83,6 +83,9 @@ SYMBOLS = {
     "gk_pack_select_bytes": (_INT, [_P, _P, _I64, ctypes.POINTER(_I64), _P]),
     "gk_pack_select": (_INT, [_P, _P, _I64, _P, _I64, _P]),
     "gk_unpack_select": (_INT, [_P, _P, _I64, _P, _P]),
+    "gk_compact": (_INT, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64), _P]),
+    "gk_class_usage": (_INT, [_P, _INT, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64),
+                              ctypes.POINTER(_I64), ctypes.POINTER(_I64), _P]),
     "gk_peek": (_INT, [ctypes.c_char_p, ctypes.POINTER(_D), ctypes.POINTER(_I64)]),
     "gk_load": (_INT, [_P, ctypes.c_char_p, _P]),
     "gk_dir_create": (_INT, [_I64, _INT, ctypes.POINTER(_P)]),

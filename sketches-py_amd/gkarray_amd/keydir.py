@@ -197,7 +197,11 @@ class KeyedStreamSet:
     owns stream ``directory.lookup([k])`` of ``streams``; both halves grow by
     doubling when a batch brings more new keys than fit.  ``remove`` is
     ``del sketches[k]``: the stream is reset and its id goes to the next new
-    key, so keys that come and go at a steady count never grow either half."""
+    key, so keys that come and go at a steady count never grow either half.
+    Removal resets the stream but, on the GPU, the stream keeps its capacity
+    class: the key that inherits the id inherits the class and its slot, until
+    ``compact()`` puts every stream back into the smallest class that holds it
+    and returns the arena memory.  Nothing compacts implicitly."""
 
     def __init__(self, eps, capacity=1024, device=None, max_streams=None):
         capacity = int(capacity)
@@ -355,10 +359,17 @@ class KeyedStreamSet:
         """``for k in keys: del sketches[k]``: the keys leave the directory,
         their streams are reset and their ids are free for new keys.
         ``KeyError`` names the first unknown key, with nothing changed; a key
-        listed twice is removed once."""
+        listed twice is removed once.  A reset stream keeps its capacity class
+        (GPU engine) until ``compact()``."""
         k = self.directory._keys(keys)
         self._release(torch.unique(self._ids(k)))
         self.directory.remove(k)
+
+    def compact(self):
+        """``streams.compact()``: after keys with large tables have gone, their
+        streams -- and the keys that inherited them -- leave the large capacity
+        classes and the memory goes back.  ``{"demoted": .., "bytes_freed": ..}``."""
+        return self.streams.compact()
 
     def discard(self, keys):
         """``remove`` that ignores keys the object does not hold (and ``NO_KEY``)."""

@@ -118,6 +118,43 @@ class StreamSet:
     def num_promoted(self):
         return self._lib.gk_num_promoted(self._h)
 
+    def class_usage(self):
+        """What the set holds per capacity class (``gk_class_usage``): a list
+        with one dict per class -- ``capacity`` (table entries of a slot),
+        ``streams`` (streams whose class it is), ``slots_used`` / ``slots_alloc``
+        (of the class's arena; class 0: both num_streams), ``arena_bytes`` and
+        ``workspace_bytes``.  The host engine has one unbounded class.  The
+        set's earlier work is settled first."""
+        out = []
+        with self._ctx():
+            cls = 0
+            while self._lib.gk_capacity(self._h, cls) > 0:
+                v = [ctypes.c_int64(0) for _ in range(5)]
+                self._check(self._lib.gk_class_usage(self._h, cls, *[ctypes.byref(x) for x in v], self._sp()))
+                out.append(dict(capacity=self._lib.gk_capacity(self._h, cls), streams=v[0].value,
+                                slots_used=v[1].value, slots_alloc=v[2].value, arena_bytes=v[3].value,
+                                workspace_bytes=v[4].value))
+                cls += 1
+        return out
+
+    def compact(self):
+        """Every stream into the smallest capacity class that holds its table
+        (``gk_compact``): streams that were reset or replaced by smaller ones
+        leave the large classes, member lists and slots become dense, and the
+        arena memory nobody needs goes back to the device.  No stream's state
+        changes by a bit.  Returns ``{"demoted": streams whose class dropped,
+        "bytes_freed": arena + workspace bytes returned}``.  Never called
+        implicitly.  On the host engine it returns the unused capacity of the
+        streams' buffers (``demoted`` is 0)."""
+        dem = ctypes.c_int64(0)
+        freed = ctypes.c_int64(0)
+        with self._ctx():
+            try:
+                self._check(self._lib.gk_compact(self._h, ctypes.byref(dem), ctypes.byref(freed), self._sp()))
+            finally:
+                self._inflight = None  # (the call synchronised)
+        return {"demoted": dem.value, "bytes_freed": freed.value}
+
     def _sp(self):
         return _stream_ptr(self.device)
 
@@ -361,7 +398,8 @@ class StreamSet:
     def reset_select(self, ids):
         """The listed streams back to ``GKArray(eps)`` (gk:21-29), the set's
         ``sketches[k] = GKArray(eps)`` (``gk_reset_select``).  On the GPU a
-        reset stream keeps its capacity class: no memory is returned."""
+        reset stream keeps its capacity class: no memory is returned until
+        ``compact()``."""
         i = self._select_ids(ids)
         K = i.numel()
         with self._ctx():
