@@ -9,16 +9,27 @@ after EVERY operation: every stream of every set with its oracle (table v by
 bit pattern, g, delta, pending values, n / min / max / sum / avg by bit
 pattern; ``select_cases.assert_all``), every stream the operation must not
 touch also with the ``export_state()`` snapshot from before the call, and every
-answer strictly (``unpinned=None``).  The one exception is an
-``ingest(sync=False)``: nothing is read after it, the next operation goes to
+answer strictly (``unpinned=None``).  The one exception is an ``ingest``,
+``ingest_keyed`` or ``rank_ingest_keyed`` left in flight (``sync=False``):
+nothing is read after it, its rank rows and fused answers wait, the next operation goes to
 the same set without a ``sync()`` or a snapshot, and the comparison after THAT
 operation covers both.  The driver checks that the first C ABI call the set
 then sees is that operation's own (``FIRST_CALL``): it is the call that
 settles the deferred streams.
 
 The model side restates nothing: the rules are those of select_cases,
-rank_cases, rollup_cases and transfer_cases (``check_query``, ``check_ranks``,
-``check_rollup``, ``oracle_fold``, ``copy.deepcopy`` for moved streams).
+rank_cases, rollup_cases, transfer_cases, rankkeyed_cases, rankingest_cases,
+keyed_cases and compact_cases (``check_query``, ``check_ranks``,
+``check_rollup``, ``oracle_fold``, ``copy.deepcopy`` for moved streams,
+``expected_rows``, ``oracle_step``, ``oracle_loop``, ``compact_checked``,
+``check_usage``).
+
+Where a stream lives is modelled by a lower bound only, ``floor[set][stream]``
+(``Sequence.update_floors``): the class a stream has reached and cannot have
+left.  A compaction must bring every stream to exactly ``fit`` of its table and
+count every stream whose floor lay above it (``compact_with_floors``); after
+every operation no class may hold fewer streams than the floors put at or above
+it (``usage_above_floors``).
 
 The event counters are counted on the model only, so the host-engine test can
 require them for exactly the sequences the device test runs.  "Large" is an
@@ -35,9 +46,12 @@ import numpy as np
 import pytest
 import torch
 
+import compact_cases as CC
 import keyed_cases as KC
 import parity_util as U
 import rank_cases as K
+import rankingest_cases as RI
+import rankkeyed_cases as Q
 import rollup_cases as R
 import select_cases as C
 from gk_oracle import OracleGK, flush_period
@@ -48,26 +62,29 @@ ALL = "all"
 # grow long: once per sequence, at a step drawn with the seed, and in its turn after an ingest left in flight)
 WEIGHTS = collections.OrderedDict([
     ("ingest", 22.0), ("ingest_keyed", 8.0), ("flush_select", 5.0), ("reset_select", 4.0),
-    ("quantiles_select", 5.0), ("stats_select", 2.0), ("ranks", 2.0), ("ranks_select", 4.0), ("cdf_select", 2.0),
-    ("flush", 3.0), ("quantiles", 2.0), ("reset", 0.0), ("merge_from", 6.0), ("rollup_from", 5.0),
-    ("rollup_by_key", 3.0), ("merge_compress", 4.0), ("take_put", 7.0), ("pack_unpack", 5.0), ("resized", 2.0),
-    ("roundtrip_state", 1.5), ("roundtrip_file", 1.5), ("roundtrip_pack", 1.5), ("void", 4.0)])
+    ("quantiles_select", 5.0), ("stats_select", 2.5), ("ranks", 2.5), ("ranks_select", 4.0), ("cdf_select", 2.5),
+    ("flush", 3.0), ("quantiles", 3.0), ("reset", 0.0), ("merge_from", 6.0), ("rollup_from", 5.0),
+    ("rollup_by_key", 3.0), ("merge_compress", 4.0), ("take_put", 7.0), ("pack_unpack", 5.0), ("resized", 2.5),
+    ("roundtrip_state", 2.0), ("roundtrip_file", 2.0), ("roundtrip_pack", 2.0), ("void", 4.0),
+    ("compact", 6.0), ("ranks_keyed", 4.0), ("cdf_keyed", 2.5), ("rank_ingest_keyed", 8.0)])
 KINDS = list(WEIGHTS)
-READ_ONLY = {"stats_select", "void"}
+READ_ONLY = {"stats_select", "void", "compact"}  # (a compaction changes where streams live, not what the model holds)
 STATE_CHANGING = [k for k in KINDS if k not in READ_ONLY and not k.startswith("roundtrip")]
 
 VOID_CALLS = ["select_id_S", "unpack_duplicate", "nan_q", "nan_threshold", "merge_other_eps", "keyed_id_S"]
 
-# model faults: the six named ones, and "drop:<kind>", which forgets the effect
+# model faults: the named ones, and "drop:<kind>", which forgets the effect
 # of an operation of that kind on one stream it changed
 NAMED_FAULTS = {
     "flush_select_skips_one": "flush_select", "merge_source_not_flushed": "merge_from",
     "reset_one_too_few": "reset_select", "put_sorted_order": "take_put",
-    "rollup_ascending_members": "rollup_from", "ingest_query_no_flush": "ingest"}
+    "rollup_ascending_members": "rollup_from", "ingest_query_no_flush": "ingest",
+    "rank_ingest_ranks_after_add": "rank_ingest_keyed", "ranks_keyed_no_flush": "ranks_keyed",
+    "rank_ingest_adds_negative_rows": "rank_ingest_keyed"}
 # and "drop_after_async:<kind>", the same only where the operation directly
 # follows an ingest left in flight
 AFTER_ASYNC_FAULTS = ["drop_after_async:" + k for k in ("quantiles_select", "ranks", "ranks_select", "flush_select",
-                                                        "merge_from")]
+                                                        "merge_from", "ranks_keyed", "cdf_keyed", "rank_ingest_keyed")]
 FAULTS = sorted(NAMED_FAULTS) + ["drop:" + k for k in STATE_CHANGING] + AFTER_ASYNC_FAULTS
 REPLACED = "fold_replaced_by_reset"  # counter key of a fold that guard_fold replaced
 
@@ -83,7 +100,8 @@ FIRST_CALL = {
     "rollup_by_key": {"gk_rollup"}, "merge_compress": {"gk_merge_compress"},
     "take_put": {"gk_pack_select_bytes"}, "pack_unpack": {"gk_pack_select_bytes"},
     "resized": {"gk_pack_select_bytes"}, "roundtrip_state": {"gk_export_sizes"}, "roundtrip_file": {"gk_save"},
-    "roundtrip_pack": {"gk_pack_bytes"},
+    "roundtrip_pack": {"gk_pack_bytes"}, "compact": {"gk_compact"}, "ranks_keyed": {"gk_ranks_keyed"},
+    "cdf_keyed": {"gk_ranks_keyed"}, "rank_ingest_keyed": {"gk_rank_ingest_keyed"},
     "void": {"gk_quantiles_select", "gk_flush_select", "gk_reset_select", "gk_stats_select", "gk_ranks_select",
              "gk_pack_select_bytes", "gk_quantiles", "gk_ranks", "gk_ingest_keyed"},
     REPLACED: {"gk_reset_select"}}
@@ -101,7 +119,12 @@ class _Recorder:
 
 EVENTS = ["reset_large", "ingest_after_reset_large", "move_large_onto_small", "move_small_onto_large",
           "keyed_into_large", "fold_dst_large", "fold_member_large_dst_small", "flush_pending_P_minus_1",
-          "flush_pending_1"]
+          "flush_pending_1", "compact_demotes", "compact_with_pending", "compact_empties_class",
+          "promoted_again_after_compact", "fold_dst_large_after_compact", "move_after_compact",
+          "keyed_rank_of_large", "rank_ingest_into_large", "rank_ingest_flush_inside_run",
+          "rank_ingest_new_values_only_negative"]
+# the calls that can be left in flight (sync=False); every kind follows each of them
+ASYNC_SOURCES = ["ingest", "ingest_keyed", "rank_ingest_keyed"]
 
 MAX_N = 1 << 24  # (the engines hold g and delta in int32; self-merges double n)
 
@@ -113,6 +136,24 @@ def class0_capacity(eps):
     return 128 if flush_period(eps) <= 128 else 2048
 
 
+def ladder(eps, caps=None):
+    """The capacities of the device's classes as the model holds them: `caps`
+    in the spelling of GK_CAPS, else the default ladder of gk_create for a
+    flush period of at most 1024."""
+    if caps is not None:
+        return [int(c.rstrip("b")) for c in caps.split(",")]
+    return [128, 2048, 32768, 1 << 20] if flush_period(eps) <= 128 else [2048, 32768, 1 << 20]
+
+
+def fit(E, caps):
+    """The smallest class that holds a table of E entries: E <= cap[t] - 1
+    (DESIGN.md "k_compact": a class keeps one entry free)."""
+    for t, cap in enumerate(caps):
+        if E <= cap - 1:
+            return t
+    raise ValueError("%d entries fit no class of %r" % (E, caps))
+
+
 def _fp(o):
     return (o.n, tuple(o.v), tuple(o.g), tuple(o.d), tuple(o.pending))
 
@@ -122,12 +163,60 @@ def _short(x):
     return x if len(x) <= 48 else x[:48] + ["... %d in all" % len(x)]
 
 
+def compact_with_floors(ss, oracles, floor, caps, what, settles=False, again=False):
+    """compact() of `ss`, whose stream s the model holds as oracles[s], in a class
+    of at least floor[s] on the ladder `caps`.  With `settles` (an ingest is in
+    flight) the bare call comes first, as the call that settles, and the checks
+    after it; else compact_cases.compact_checked.  On the device engine the
+    classes afterwards are predicted exactly -- class after = min(class before,
+    fit(E)), and a stream always fits its class: fit(E) -- and every stream
+    whose floor lies above its fit must be counted in `demoted`.  With `again`
+    a second compaction follows, which finds nothing to do.  Returns the
+    first call's result."""
+    fits = [fit(len(o.v), caps) for o in oracles]
+    down = sum(1 for f, t in zip(floor, fits) if f > t)
+    if settles:
+        res = ss.compact()
+        assert sorted(res) == ["bytes_freed", "demoted"], what
+        use = CC.check_usage(ss, what)
+        assert all(u["slots_used"] == u["streams"] for u in use[1:]), (what, use)
+    else:
+        res = CC.compact_checked(ss, oracles, what)
+    if not ss.is_cpu:
+        assert CC.per_class(ss) == [fits.count(c) for c in range(len(caps))], (what, fits)
+        assert ss.num_promoted == sum(1 for f in fits if f > 0), what
+        assert res["demoted"] >= down, (what, res, down)
+    if again:
+        use = ss.class_usage()
+        assert CC.compact_checked(ss, oracles, what + ", again") == CC.ZERO, what
+        assert ss.class_usage() == use, what
+    return res
+
+
+def usage_above_floors(ss, floor, caps, what):
+    """class_usage() of `ss`: its invariants, and no stream below its floor -- for every class c at least as
+    many streams in the classes >= c as the model holds there."""
+    use = CC.check_usage(ss, what)
+    if ss.is_cpu:
+        return
+    assert len(use) == len(caps), (what, use)
+    for c in range(len(use)):
+        at_least = sum(1 for f in floor if f >= c)
+        got = sum(u["streams"] for u in use[c:])
+        assert got >= at_least, "%s: %d streams in classes >= %d, the model holds %d there" % (what, got, c, at_least)
+
+
 class Sequence:
-    def __init__(self, dev, eps, seed, nops, sizes, async_ingest, via_host, stop_after, model_fault):
+    def __init__(self, dev, eps, seed, nops, sizes, async_ingest, via_host, stop_after, model_fault, caps=None,
+                 weights=None):
         from gkarray_amd import StreamSet
         self.StreamSet = StreamSet
         self.dev, self.eps, self.seed, self.nops = dev, eps, seed, nops
         self.async_ingest, self.via_host = async_ingest, via_host
+        self.caps = ladder(eps, caps)
+        w = dict(WEIGHTS, **(weights or {}))
+        assert set(w) == set(KINDS), sorted(set(w) - set(KINDS))
+        self.weights = np.asarray([w[x] for x in KINDS])
         self.steps = nops if stop_after is None else min(nops, stop_after)
         assert model_fault is None or model_fault in FAULTS, model_fault
         self.fault = model_fault
@@ -141,14 +230,22 @@ class Sequence:
         self.rng = np.random.default_rng([int(seed), self.P])
         self.reset_step = int(self.rng.integers(nops // 3, max(nops, nops // 3 + 1)))
         self.sets = [U._ss(S, eps, dev) for S in sizes]
+        assert self.caps[0] == self.cap0
         if dev != "cpu":
-            assert all(ss.capacity(0) == self.cap0 for ss in self.sets)
+            for ss in self.sets:  # the model's ladder is the device's
+                assert [ss.capacity(c) for c in range(len(self.caps) + 1)] == self.caps + [-1]
         self.orc = [[OracleGK(eps) for _ in range(S)] for S in sizes]
+        # floor[set][stream]: a class the stream has reached and cannot have left (see update_floors)
+        self.floor = [[0] * S for S in sizes]
+        self.renew_floor = set()     # sets that came back new (resized, a round trip) or gave everything back
+        self.compacted = set()       # sets that have been compacted since they were made
+        self.demoted = set()         # (set, stream) positions a compaction demoted, until they are promoted again
         self.snap = [None] * len(sizes)
         self.after_async = None      # index of the set whose ingest was left in flight
+        self.async_source = None     # and the kind of that ingest
         self.follows_async = False   # this step is the one right after it
         self.replaced = False        # this step's fold was replaced by a reset (guard_fold)
-        self.async_count = 0
+        self.async_count = collections.Counter()  # per source
         self.late_answers = []       # (tensor, expected, what) of fused queries left in flight
         self.was_reset_large = set()  # (set, stream) positions
         self.nruns = 0
@@ -252,13 +349,33 @@ class Sequence:
         if oracles is not None:
             self.orc[a] = oracles
         self.snap[a] = None
+        self.forget_classes(a)
+        self.compacted.discard(a)
+
+    def forget_classes(self, a):
+        """Set a is a new one, or gave every class back: its floors start again."""
+        self.renew_floor.add(a)
         self.was_reset_large = {(i, s) for i, s in self.was_reset_large if i != a}
+        self.demoted = {(i, s) for i, s in self.demoted if i != a}
+
+    def left_in_flight(self, a, source):
+        self.after_async, self.async_source = a, source
+        self.async_count[source] += 1
+
+    def late(self, check):
+        """A comparison of outputs left in flight: made after the next operation."""
+        self.late_answers.append(check)
 
     def note_ingest(self, a, streams):
         for s in streams:
             if (a, s) in self.was_reset_large:
                 self.was_reset_large.discard((a, s))
                 self.events["ingest_after_reset_large"] += 1
+
+    def note_fold_dst_large(self, a):
+        self.events["fold_dst_large"] += 1
+        if a in self.compacted:
+            self.events["fold_dst_large_after_compact"] += 1
 
     def note_move(self, src_o, dst_o):
         if self.large(src_o) and not self.large(dst_o):
@@ -315,22 +432,25 @@ class Sequence:
                 exp = C.oracle_answers(copy.deepcopy(orc), range(S), qs, single)
             else:
                 exp = C.oracle_answers(orc, range(S), qs, single)
-            if sync:
-                U.assert_same_quantiles(got.cpu().numpy(), exp, "fused answers", None)
-            else:
-                self.late_answers.append((got, exp, "fused answers of step %d" % (len(self.log) - 1)))
+            self.fused_answers(got, exp, sync)
         if not sync:
-            self.after_async = a
-            self.async_count += 1
+            self.left_in_flight(a, "ingest")
         return {a: ALL}, any(lens)
 
-    def op_ingest_keyed(self, a, args):
-        rng, ss, orc = self.rng, self.sets[a], self.orc[a]
-        S = ss.num_streams
-        vseed = int(rng.integers(1 << 30))
-        vr = np.random.default_rng(vseed)
-        r = rng.random()
-        N = 0 if r < 0.1 else int(vr.integers(1, 4)) if r < 0.2 else int(vr.integers(S, 6 * self.P + S))
+    def fused_answers(self, got, exp, sync):
+        what = "fused answers of step %d" % (len(self.log) - 1)
+        check = lambda: U.assert_same_quantiles(got.cpu().numpy(), exp, what, None)  # noqa: E731
+        if sync:
+            check()
+        else:
+            self.late(check)
+
+    def keyed_ids(self, a, vr, N, none=0.0):
+        """The stream ids of N keyed samples: random ones, one stream (a large one
+        preferred) or a subset of the streams, about 3 % of them negative; with
+        probability `none` every one is negative."""
+        rng, orc = self.rng, self.orc[a]
+        S = len(orc)
         mode = ["random", "one", "subset"][int(rng.integers(0, 3))]
         if mode == "random":
             ids = vr.integers(0, S, N)
@@ -341,20 +461,35 @@ class Sequence:
             ids = vr.choice(vr.choice(S, max(1, S // 3), replace=False), N)
         ids = np.asarray(ids, dtype=np.int64)
         ids[vr.random(N) < 0.03] = -1  # (skipped by the call)
+        if rng.random() < none:
+            mode = "none"
+            ids = -1 - np.asarray(vr.integers(0, 9, N), dtype=np.int64)
+        return mode, ids
+
+    def op_ingest_keyed(self, a, args):
+        rng, ss, orc = self.rng, self.sets[a], self.orc[a]
+        S = ss.num_streams
+        vseed = int(rng.integers(1 << 30))
+        vr = np.random.default_rng(vseed)
+        r = rng.random()
+        N = 0 if r < 0.1 else int(vr.integers(1, 4)) if r < 0.2 else int(vr.integers(S, 6 * self.P + S))
+        mode, ids = self.keyed_ids(a, vr, N)
         vals = self.values(vr, N)
         query = rng.random() < 0.3
         qs, single = self.qs() if query else (None, False)
+        sync = not (self.async_ingest and rng.random() < 0.7)
         args.update(vseed=vseed, N=N, mode=mode, streams=_short(sorted(set(ids[ids >= 0].tolist()))), qs=qs,
-                    single=single)
+                    single=single, sync=sync)
         hit = sorted(set(ids[ids >= 0].tolist()))
         if any(self.large(orc[s]) for s in hit):
             self.events["keyed_into_large"] += 1
-        got = ss.ingest_keyed(self.ids_t(ids), self.t(vals, np.float64), quantiles=qs, single=single)
+        got = ss.ingest_keyed(self.ids_t(ids), self.t(vals, np.float64), quantiles=qs, single=single, sync=sync)
         self.note_ingest(a, hit)
         KC.oracle_loop(orc, ids, vals)
         if query:
-            U.assert_same_quantiles(got.cpu().numpy(), C.oracle_answers(orc, range(S), qs, single),
-                                    "fused answers", None)
+            self.fused_answers(got, C.oracle_answers(orc, range(S), qs, single), sync)
+        if not sync:
+            self.left_in_flight(a, "ingest_keyed")
         return {a: ALL}, bool(hit)
 
     # ---------------------------------------------------------------- selection
@@ -437,6 +572,191 @@ class Sequence:
         U.assert_same_quantiles(got, exp.reshape(got.shape), "cdf_select", None)
         return {a: set(ids)}, any(orc[s].n for s in ids)
 
+    # ------------------------------------------------------- keyed rank queries
+    def keyed_batch(self, a, args, thresholds, none=0.05):
+        """(ids, xs) of a keyed rank query or score-and-ingest on set a.  The x of
+        a row is one of self.xs of its stream (`thresholds`) or a value to be
+        ingested; a negative row has a NaN x at times."""
+        rng, orc = self.rng, self.orc[a]
+        S, P = len(orc), self.P
+        vseed = int(rng.integers(1 << 30))
+        vr = np.random.default_rng(vseed)
+        r = rng.random()
+        top = 3 * P if P <= 128 else 2 * P  # (a few flush periods)
+        N = 0 if r < 0.1 else int(vr.integers(1, 4)) if r < 0.2 else int(vr.integers(S, top + S))
+        mode, ids = self.keyed_ids(a, vr, N, none=none)
+        live = sorted(set(ids[ids >= 0].tolist()))
+        if thresholds:
+            per = {s: self.xs(a, [s]) for s in live}
+            pick = vr.integers(0, 6, N)
+            xs = np.asarray([per[s][k % len(per[s])] if s >= 0 else 0.5 for s, k in zip(ids.tolist(), pick.tolist())],
+                            dtype=np.float64)
+        else:
+            xs = self.values(vr, N)
+        xs[(ids < 0) & (vr.random(N) < 0.5)] = float("nan")
+        args.update(vseed=vseed, N=N, mode=mode, streams=_short(live))
+        return ids, xs, live
+
+    def rank_outputs(self, allow_none):
+        combos = [(True, True, False), (True, True, True), (True, False, True), (False, True, False),
+                  (False, False, True)] + ([(False, False, False)] if allow_none else [])
+        return combos[int(self.rng.integers(0, len(combos)))]
+
+    def same_rows(self, got, exp, want, what):
+        for g, e, w, name in zip(got, exp or (None,) * 3, want, ("lo", "hi", "n")):
+            assert (g is None) == (not w), (what, name)
+            if w:
+                Q.same_i64(g, e, what + " " + name)
+
+    def score_of(self, rows):
+        lo, hi, n = rows
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (lo + hi).astype(np.float64) / (2.0 * n.astype(np.float64))
+
+    def op_ranks_keyed(self, a, args, cdf=False):
+        ss, orc = self.sets[a], self.orc[a]
+        ids, xs, live = self.keyed_batch(a, args, thresholds=True)
+        want = (True, True, True) if cdf else self.rank_outputs(False)
+        args.update(want=want)
+        if any(self.large(orc[s]) for s in live):
+            self.events["keyed_rank_of_large"] += 1
+        self.note_flush([orc[s] for s in live])
+        ti, tx = self.ids_t(ids), self.t(xs, np.float64)
+        if cdf:
+            got = ss.cdf_keyed(ti, tx)
+        else:
+            got = ss.ranks_keyed(ti, tx, lo=want[0], hi=want[1], n=want[2])
+        model = copy.deepcopy(orc) if self.fault == "ranks_keyed_no_flush" else orc
+        K.flush_covered(model, live)  # (the state change: the occurring streams are flushed)
+        exp = Q.expected_rows(model, ids.tolist(), xs.tolist())
+        if cdf:
+            assert got.dtype == torch.float64 and tuple(got.shape) == (len(ids),)
+            U.assert_same_quantiles(got.cpu().numpy(), self.score_of(exp), "cdf_keyed", None)
+        else:
+            self.same_rows(got, exp, want, "ranks_keyed")
+        return {a: set(live)}, any(orc[s].n for s in live)
+
+    def op_cdf_keyed(self, a, args):
+        return self.op_ranks_keyed(a, args, cdf=True)
+
+    def op_rank_ingest_keyed(self, a, args):
+        rng, ss, orc = self.rng, self.sets[a], self.orc[a]
+        S = len(orc)
+        ids, xs, live = self.keyed_batch(a, args, thresholds=False, none=0.12)
+        query = rng.random() < 0.3
+        qs, single = self.qs() if query else (None, False)
+        score = bool(rng.random() < 0.5)
+        want = (True, True, True) if score else self.rank_outputs(True)
+        sync = not (self.async_ingest and rng.random() < 0.7)
+        args.update(qs=qs, single=single, score=score, want=want, sync=sync)
+        if any(self.large(orc[s]) for s in live):
+            self.events["rank_ingest_into_large"] += 1
+        if live and np.bincount(ids[ids >= 0]).max() >= self.P:
+            self.events["rank_ingest_flush_inside_run"] += 1
+        if len(ids) and not live:
+            self.events["rank_ingest_new_values_only_negative"] += 1
+        ranked = any(want)  # (with no rank output the call is ingest_keyed: nothing is flushed first)
+        if ranked:
+            self.note_flush([orc[s] for s in live])
+        ti, tx = self.ids_t(ids), self.t(xs, np.float64)
+        if score:
+            got = ss.score_ingest_keyed(ti, tx, quantiles=qs, single=single, sync=sync)
+            got = got if query else (got,)
+        else:
+            got = ss.rank_ingest_keyed(ti, tx, lo=want[0], hi=want[1], n=want[2], quantiles=qs, single=single,
+                                       sync=sync)
+        self.note_ingest(a, live)
+        il, xl = ids.tolist(), xs.tolist()
+        if not ranked:
+            exp = None
+            KC.oracle_loop(orc, ids, xs)
+        elif self.fault == "rank_ingest_ranks_after_add":
+            ahead = copy.deepcopy(orc)
+            KC.oracle_loop(ahead, ids, xs)
+            K.flush_covered(ahead, live)
+            exp = Q.expected_rows(ahead, il, xl)
+            RI.oracle_step(orc, il, xl)
+        else:
+            exp = RI.oracle_step(orc, il, xl)  # every row against the state before the batch, then the batch
+        if self.fault == "rank_ingest_adds_negative_rows":
+            for s, x in zip(il, xl):
+                if s < 0 and x == x:
+                    orc[(-1 - s) % S].add(x)
+        checks = []
+        if score:
+            exp_score = self.score_of(exp)
+            checks.append(lambda: U.assert_same_quantiles(got[0].cpu().numpy(), exp_score, "score_ingest_keyed", None))
+        else:
+            checks.append(lambda: self.same_rows(got[:3], exp, want, "rank_ingest_keyed"))
+        if query:
+            exp_q = C.oracle_answers(orc, range(S), qs, single)
+            checks.append(lambda: U.assert_same_quantiles(got[-1].cpu().numpy(), exp_q, "fused answers", None))
+        for check in checks:
+            if sync:
+                check()
+            else:
+                self.late(check)
+        if not sync:
+            self.left_in_flight(a, "rank_ingest_keyed")
+        return {a: ALL if query else set(live)}, bool(live)
+
+    # --------------------------------------------------------------- compaction
+    def fits(self, a):
+        return [fit(len(o.v), self.caps) for o in self.orc[a]]
+
+    def op_compact(self, a, args):
+        rng, ss, orc = self.rng, self.sets[a], self.orc[a]
+        fits, floor = self.fits(a), self.floor[a]
+        down = [s for s in range(len(orc)) if floor[s] > fits[s]]
+        again = bool(rng.random() < 1.0 / 3.0)
+        args.update(demotes=_short(down), again=again)
+        if down:
+            self.events["compact_demotes"] += 1
+        if any(o.pending for o, f in zip(orc, floor) if f > 0):
+            self.events["compact_with_pending"] += 1
+        if any(c not in fits for c in set(floor) if c > 0):
+            self.events["compact_empties_class"] += 1
+        compact_with_floors(ss, orc, floor, self.caps, "compact of set %d" % a, settles=self.follows_async, again=again)
+        self.floor[a] = list(fits)
+        self.demoted |= {(a, s) for s in down}
+        self.was_reset_large = {(i, s) for i, s in self.was_reset_large if i != a}
+        self.compacted.add(a)
+        return {a: set()}, bool(down)
+
+    def update_floors(self):
+        """floor[set][stream] after an operation: the maximum of itself and fit of
+        the oracle's table -- classes only grow, and a stream always fits its
+        class.  A set that came back new or gave everything back starts at fit of
+        the present tables (a sound lower bound whatever an import chose); a
+        compaction has set its floors itself.  reset_select, put and
+        unpack_select demote nothing: the floor stays."""
+        for a, orc in enumerate(self.orc):
+            fits = self.fits(a)
+            if a in self.renew_floor:
+                self.floor[a] = fits
+                continue
+            floor = self.floor[a]
+            for s, f in enumerate(fits):
+                if f > floor[s]:
+                    floor[s] = f
+                    if (a, s) in self.demoted:
+                        self.demoted.discard((a, s))
+                        self.events["promoted_again_after_compact"] += 1
+        self.renew_floor.clear()
+        # the model's own books agree: a stream fits the class of its floor, and
+        # a stream that was reset while large still holds a class above 0
+        for a, orc in enumerate(self.orc):
+            for s, o in enumerate(orc):
+                assert len(o.v) <= self.caps[self.floor[a][s]] - 1, \
+                    "model: stream %d of set %d outgrew its floor" % (s, a)
+                if len(o.v) in self.caps:
+                    self.events["table_at_capacity"] += 1
+        for a, s in self.was_reset_large:
+            assert self.floor[a][s] > 0, "model: stream %d of set %d was reset while large, floor 0" % (s, a)
+
+    def check_classes(self, a, what):
+        usage_above_floors(self.sets[a], self.floor[a], self.caps, what)
+
     # ---------------------------------------------------------------- whole set
     def op_flush(self, a, args):
         self.note_flush(self.orc[a])
@@ -456,6 +776,7 @@ class Sequence:
     def op_reset(self, a, args):
         self.sets[a].reset()
         self.orc[a] = [OracleGK(self.eps) for _ in self.orc[a]]
+        self.forget_classes(a)  # (a whole-set reset gives every class back)
         return {a: ALL}, None
 
     # -------------------------------------------------------------------- folds
@@ -508,7 +829,7 @@ class Sequence:
         for k in range(m):
             d = oa[ids_a[k]]
             if self.large(d):
-                self.events["fold_dst_large"] += 1
+                self.note_fold_dst_large(a)
             elif "b" in plan and self.large(ob[ids_b[k]]):
                 self.events["fold_member_large_dst_small"] += 1
         ta = A if A.num_streams == m else A.take(C.i32(ids_a))
@@ -557,7 +878,7 @@ class Sequence:
             return touched, None
         for j, g in enumerate(groups):
             if g and self.large(oa[j]):
-                self.events["fold_dst_large"] += 1
+                self.note_fold_dst_large(a)
             elif any(self.large(ob[m]) for m in g):
                 self.events["fold_member_large_dst_small"] += 1
         dst, src = self.sets[a], self.sets[b]
@@ -638,6 +959,8 @@ class Sequence:
         dst = self.pick_ids(b, distinct=True, count=len(src))
         for s, d in zip(src, dst):
             self.note_move(self.orc[a][s], self.orc[b][d])
+        if src and (a in self.compacted or b in self.compacted):
+            self.events["move_after_compact"] += 1
         return src, dst
 
     def model_move(self, a, b, src, dst, sorted_order=False):
@@ -792,7 +1115,7 @@ class Sequence:
     # --------------------------------------------------------------- the driver
     def step(self, k):
         rng = self.rng
-        w = np.asarray([WEIGHTS[x] for x in KINDS])
+        w = self.weights
         kind = KINDS[int(rng.choice(len(KINDS), p=w / w.sum()))]
         a = int(rng.integers(0, len(self.sets)))
         if k == self.reset_step:
@@ -800,12 +1123,16 @@ class Sequence:
         if kind in ("flush", "flush_select") and rng.random() < 0.7:
             # (a flush matters where values are pending: the set with most such streams)
             a = max(range(len(self.sets)), key=lambda i: (sum(1 for o in self.orc[i] if o.pending), -i))
+        if kind == "compact" and rng.random() < 0.7:
+            # (a compaction matters where streams have shrunk: the set with most of them)
+            a = max(range(len(self.sets)),
+                    key=lambda i: (sum(1 for f, t in zip(self.floor[i], self.fits(i)) if f > t), -i))
         follows_async = self.follows_async = self.after_async is not None
         self.replaced = False
         if follows_async:
             # straight to the set whose ingest is in flight, every kind in turn
-            a = self.after_async
-            kind = KINDS[(7 * self.seed + self.async_count) % len(KINDS)]
+            a, source = self.after_async, self.async_source
+            kind = KINDS[(7 * self.seed + self.async_count[source]) % len(KINDS)]
             self.after_async = None
         args = {"set": a}
         self.log.append((k, kind, args))
@@ -830,6 +1157,7 @@ class Sequence:
         self.ran[counted] += 1
         if follows_async:
             self.events["after_async:" + counted] += 1
+            self.events["after_async:%s:%s" % (source, counted)] += 1
         if effective is None:  # a state-changing kind: did the model change?
             effective = [[_fp(o) for o in os_] for os_ in self.orc] != before
         self.effective[counted] += bool(effective)
@@ -838,6 +1166,8 @@ class Sequence:
         sizes = [len(o.v) for os_ in self.orc for o in os_]
         self.max_table = max(self.max_table, max(sizes))
         self.max_large = max(self.max_large, sum(1 for x in sizes if x > self.cap0))
+        if kind != "compact":
+            self.update_floors()
         if self.after_async is not None:
             # nothing is read between an ingest left in flight and the next operation,
             # and that operation finds no snapshot of the set to compare with
@@ -848,12 +1178,13 @@ class Sequence:
             if listed is ALL or follows_async and i == a:
                 listed = set(range(ss.num_streams))
             self.snap[i] = C.assert_all(ss, self.orc[i], "after %s, set %d" % (kind, i), self.snap[i], listed)
+            self.check_classes(i, "after %s, set %d" % (kind, i))
         self.check_late_answers()
 
     def check_late_answers(self):
         late, self.late_answers = self.late_answers, []
-        for got, exp, what in late:
-            U.assert_same_quantiles(got.cpu().numpy(), exp, what, None)
+        for check in late:
+            check()
 
     def forget_one(self, saved, before):
         """The generic model fault: the last stream this operation changed goes back to its state before."""
@@ -893,11 +1224,12 @@ class Sequence:
 
 
 def run_sequence(dev, eps, seed, nops, sizes=(24, 16, 7), async_ingest=False, via_host=False, stop_after=None,
-                 model_fault=None):
+                 model_fault=None, caps=None, weights=None):
     """One sequence of `nops` operations, reproducible from (eps, seed) and the
     keyword settings; `stop_after` ends it after that many steps (replay of a
     failure up to the step before it).  Returns the model-side counters."""
-    return Sequence(dev, eps, seed, nops, tuple(sizes), async_ingest, via_host, stop_after, model_fault).run()
+    return Sequence(dev, eps, seed, nops, tuple(sizes), async_ingest, via_host, stop_after, model_fault, caps,
+                    weights).run()
 
 
 # ------------------------------------------------------------- configurations
@@ -906,15 +1238,24 @@ def run_sequence(dev, eps, seed, nops, sizes=(24, 16, 7), async_ingest=False, vi
 SHORT_LADDER = "128,256,512,4096b"
 CONFIGS = collections.OrderedDict([
     ("default", dict(eps=[0.1, 0.01], env={}, kw={}, nops=130, gpu_seeds=[1, 2, 3], cpu_seeds=[4, 5])),
-    ("short_ladder", dict(eps=[0.01], env={"GK_CAPS": SHORT_LADDER}, kw={}, nops=130, gpu_seeds=[11, 12, 13, 14],
-                          cpu_seeds=[15, 16])),
+    ("short_ladder", dict(eps=[0.01], env={"GK_CAPS": SHORT_LADDER}, kw=dict(caps=SHORT_LADDER), nops=130,
+                          gpu_seeds=[11, 12, 13, 14], cpu_seeds=[15, 16])),
+    # (six seeds: every kind follows each of the three calls left in flight, 81 pairs)
     ("tiny_arenas", dict(eps=[0.01], env={"GK_CAPS": SHORT_LADDER, "GK_POOL_SLOTS": "2"},
-                         kw=dict(async_ingest=True), nops=130, gpu_seeds=[21, 22, 23, 24],
-                         cpu_seeds=[25, 26])),
-    ("no_small_class", dict(eps=[0.001], env={}, kw=dict(sizes=(8, 6, 4)), nops=120, gpu_seeds=[31, 32, 33, 36],
+                         kw=dict(async_ingest=True, caps=SHORT_LADDER,
+                                 weights=dict(ingest=18.0, ingest_keyed=15.0, rank_ingest_keyed=14.0)),
+                         nops=130, gpu_seeds=[21, 22, 23, 24, 27, 37], cpu_seeds=[25, 26])),
+    ("no_small_class", dict(eps=[0.001], env={}, kw=dict(sizes=(8, 6, 4)), nops=120, gpu_seeds=[31, 32, 33, 36, 41],
                             cpu_seeds=[34, 35])),
-    ("via_host", dict(eps=[0.01], env={}, kw=dict(via_host=True), nops=130, gpu_seeds=[41, 42, 43, 44],
+    ("via_host", dict(eps=[0.01], env={}, kw=dict(via_host=True), nops=130, gpu_seeds=[41, 42, 43, 44, 48],
                       cpu_seeds=[45])),
+    # 64-sample chunks of k_rank_keyed / k_rank_ingest_keyed at batches of a few hundred samples: runs of one
+    # stream start on, straddle and span a chunk; the keyed kinds weighted up, ingests left in flight
+    ("keyed_chunks", dict(eps=[0.01], env={"GK_CAPS": SHORT_LADDER, "GK_RANKK_CHUNK": "64"},
+                          kw=dict(async_ingest=True, caps=SHORT_LADDER,
+                                  weights=dict(ingest_keyed=14.0, ranks_keyed=10.0, cdf_keyed=5.0,
+                                               rank_ingest_keyed=18.0)),
+                          nops=130, gpu_seeds=[51, 53, 55, 56, 58], cpu_seeds=[52])),
 ])
 LAST_BOUNDED_CAPACITY = 512  # of SHORT_LADDER: the class above it is the unbounded kernel's
 
@@ -926,6 +1267,9 @@ def runs(name, seeds):
 
 def required_events(name):
     ev = list(EVENTS)
+    if all(class0_capacity(eps) == 128 for eps in CONFIGS[name]["eps"]):
+        ev.append("table_at_capacity")  # (a table of exactly cap[t] entries: the first that does not fit class t)
     if CONFIGS[name]["kw"].get("async_ingest"):
         ev += ["after_async:" + k for k in KINDS]
+        ev += ["after_async:%s:%s" % (src, k) for src in ASYNC_SOURCES for k in KINDS]
     return ev

@@ -45,7 +45,9 @@ def totals(name):
 @pytest.mark.parametrize("name", list(O.CONFIGS))
 def test_opseq_coverage_of_the_device_seeds(name):
     """Conditions, not measurements, over the seeds the device test runs: every
-    operation kind effective at least 3 times, every event at least once, more
+    operation kind effective at least 3 times (a compaction: the model predicts
+    a demotion), every event at least once (with ingests left in flight: every
+    kind directly after each of the three calls that can be), more
     streams large at once than GK_POOL_SLOTS=2 has slots, and on the short
     ladder a table beyond the last bounded class."""
     ran, eff, ev, top, large = totals(name)
@@ -58,6 +60,18 @@ def test_opseq_coverage_of_the_device_seeds(name):
     if "GK_CAPS" in O.CONFIGS[name]["env"]:
         assert top > O.LAST_BOUNDED_CAPACITY
         assert top < 4095  # (the ladder's last class holds one entry less than its capacity)
+
+
+def test_fit_boundaries():
+    """fit(E): the smallest class t with E <= cap[t] - 1, at the table sizes of
+    compact_cases.case_fit_boundaries on 128,256,512,4096."""
+    caps = O.ladder(0.01, O.SHORT_LADDER)
+    assert caps == [128, 256, 512, 4096]
+    assert [O.fit(E, caps) for E in (0, 1, 127, 128, 255, 256, 511, 512)] == [0, 0, 0, 1, 1, 2, 2, 3]
+    assert O.fit(4095, caps) == 3
+    with pytest.raises(ValueError):
+        O.fit(4096, caps)
+    assert O.ladder(0.01) == [128, 2048, 32768, 1 << 20] and O.ladder(0.001) == [2048, 32768, 1 << 20]
 
 
 def test_opseq_is_reproducible_and_replayable():

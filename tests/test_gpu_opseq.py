@@ -54,3 +54,10 @@ def test_opseq_no_small_class(gpu_device, monkeypatch, eps, seed):
 def test_opseq_via_host(gpu_device, monkeypatch, eps, seed):
     """Moves through the host engine and back."""
     _run(gpu_device, monkeypatch, "via_host", eps, seed)
+
+
+@pytest.mark.parametrize("eps,seed", O.runs("keyed_chunks", "gpu_seeds"))
+def test_opseq_keyed_chunks(gpu_device, monkeypatch, eps, seed):
+    """64-sample chunks of the two keyed rank kernels on the short ladder, the keyed kinds weighted up,
+    keyed ingests and score-and-ingests left in flight."""
+    _run(gpu_device, monkeypatch, "keyed_chunks", eps, seed)
